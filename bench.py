@@ -33,10 +33,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-# the step overlaps two HIP streams (train_step.py); ROCm multiplexes streams onto a few hardware queues and
-# RCCL adds its own -- keep enough queues that the two compute streams never share one (measured: sharing
-# costs 10 % of the step).  Must be set before the HIP runtime initialises.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 # multi-process GPU work on this pool needs dmabuf IPC (RCCL otherwise fails with hipIpcGetMemHandle: invalid argument)
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 
@@ -92,6 +88,9 @@ def parse():
                     help='the timed steps and nothing else: no roofline section, no in-step probe steps, no fp32 line, no CPU baseline '
                          '(A/B runs; profiler runs whose per-kernel table must be the step only).  The line then carries no roofline: not the contract line')
     ap.add_argument('--trace-losses', action='store_true', help='print every step\'s losses to stderr (debug)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, or float64 '
+                         'where the step computed float64; at most 64 MB, see dump_outputs) to compare two builds output for output')
     return ap.parse_args()
 
 
@@ -198,6 +197,48 @@ def kernel_source_sha16():
         h.update(os.path.basename(f).encode())
         h.update(open(f, 'rb').read())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMS = 1 << 20
+
+
+def _flatten_outputs(out, prefix=''):
+    """(name, value) pairs of a nested dict of tensors / numbers; nested keys are joined with '.'."""
+    if isinstance(out, dict):
+        for k in sorted(out):
+            yield from _flatten_outputs(out[k], '%s%s.' % (prefix, k))
+    else:
+        yield prefix[:-1], out
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: every array of `out` (what the timed path returned in its last step) as path/<name>.npy, float64 where
+    the path computed float64 and float32 otherwise.  When the whole arrays would exceed 64 MB, each array of more than 2^20
+    elements is replaced by the same fixed sample of 2^20 of its elements (flattened C order, indices drawn by numpy's
+    default_rng(0) and sorted), so two builds still compare element for element."""
+    import numpy as np
+    import torch
+    arrays = []
+    for name, v in _flatten_outputs(out):
+        t = v.detach() if torch.is_tensor(v) else torch.as_tensor(v)
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        arrays.append((name, t.cpu().numpy()))
+    if sum(a.nbytes for _, a in arrays) > DUMP_LIMIT_BYTES:
+        sampled = []
+        for name, a in arrays:
+            if a.size > DUMP_SAMPLE_ELEMS:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE_ELEMS, replace=False))
+                a = a.reshape(-1)[idx]
+            sampled.append((name, a))
+        arrays = sampled
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs: %d arrays need %.1f MB, more than the 64 MB limit' % (len(arrays), total / 2 ** 20))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(path, name + '.npy'), a)
+    print('bench.py: wrote %d arrays (%.1f MB) to %s' % (len(arrays), total / 2 ** 20, path), file=sys.stderr)
 
 
 def _time_launches(fn, iters=50):
@@ -534,6 +575,8 @@ def run_inference(args, device):
         out = run()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     roof = None
     if not args.step_only:
         # the workload's dominant kernel in isolation at THIS batch (RAB conv1 fprop, 36 of the forward's 78 conv launches): at B = 16 a
@@ -568,6 +611,7 @@ def run_chain(args, device):
     B = args.batch
     scales = [int(v) for v in args.scales.split(',')]
     per, tot_t, tot_img = {}, 0.0, 0
+    last_outs = {}
     for i, sc in enumerate(scales):
         torch.manual_seed(20240 + sc)
         G = M.GeneratorResNet(M.ResGroup, n_residual_blocks=12, n_basic_blocks=3, upscale_factor=sc)
@@ -598,6 +642,8 @@ def run_chain(args, device):
             out = step(lr, hr, alpha)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            last_outs['x%d' % sc] = {k: v.detach().cpu() for k, v in out.items()}     # before the next scale reuses the buffers
         finite = all(_math.isfinite(float(out[k])) for k in ('loss_G', 'loss_D'))
         gf = GF_PER_IMG_ITER_BY_SCALE.get(sc)
         per['x%d' % sc] = {'img_per_s': round(B * args.steps / dt, 2), 'ms_per_step': round(dt / args.steps * 1e3, 2), 'lr_side': side,
@@ -608,6 +654,8 @@ def run_chain(args, device):
         if os.environ.get('BENCH_CHAIN_EMPTY_CACHE', '0') == '1':
             torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_outs)
     math = ops.get_conv_math()
     print(json.dumps({'metric': 'chain-training images/sec over the scale sweep (HR 216x216 tiles)', 'value': round(tot_img / tot_t, 2),
                       'unit': 'img/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
@@ -641,7 +689,7 @@ def run_sibling(args, device):
         oD = torch.optim.Adam(D.parameters(), lr=2e-4, betas=(0.9, 0.999))
         hr = torch.rand(B, 3, LR_SIDE * SCALE, LR_SIDE * SCALE, generator=gen).to(device)
         lr = torch.rand(B, 3, LR_SIDE, LR_SIDE, generator=gen).to(device)
-        run = lambda: M.train_step(G, D, Fx, oG, oD, lr, hr)['loss_G']
+        run = lambda: M.train_step(G, D, Fx, oG, oD, lr, hr)
         name = 'SRGAN x4 training step (G 16 blocks + D + VGG features, LSGAN), LR 54x54 -> HR 216x216, batch %d' % B
     elif args.workload == 'sragan':
         # SRAGAN's iteration is SRADSGAN's (sragan.py:539-575) around its own generator (12 residual blocks x 5 basic
@@ -663,7 +711,7 @@ def run_sibling(args, device):
         hr = torch.rand(B, 3, LR_SIDE * SCALE, LR_SIDE * SCALE, generator=gen).to(device)
         lr = torch.rand(B, 3, LR_SIDE, LR_SIDE, generator=gen).to(device)
         alpha = torch.rand(B, 1, 1, 1, generator=gen).to(device)
-        run = lambda: step(lr, hr, alpha)['loss_G']
+        run = lambda: step(lr, hr, alpha)
         name = ('SRAGAN x4 training step (G 12x5 attention blocks + D + VGG features, WGAN-GP), LR 54x54 -> HR 216x216, '
                 'batch %d' % B)
     else:
@@ -680,7 +728,7 @@ def run_sibling(args, device):
             loss = (net(lr) - hr).abs().mean()
             loss.backward()
             opt.step()
-            return loss.detach()
+            return {'loss': loss.detach()}
         name = 'EDSR x2 L1 training step (Net(3,256,32,2), BASELINE configs[0]), LR 108x108 -> HR 216x216, batch %d' % B
     for _ in range(max(0, args.spinup_steps) + args.warmup):    # untimed spin-up + warm-up
         out = run()
@@ -690,11 +738,13 @@ def run_sibling(args, device):
         out = run()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     print(json.dumps({'metric': 'training images/sec (216x216 HR tiles)', 'value': round(B * args.steps / dt, 2),
                       'unit': 'img/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
                       'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'dtype': 'f32',
                       'data': 'synthetic', 'config': {'workload': name, 'conv_math': ops.get_conv_math()},
-                      'last_loss': round(float(out), 6)}), flush=True)
+                      'last_loss': round(float(out['loss_G'] if 'loss_G' in out else out['loss']), 6)}), flush=True)
 
 
 def cpu_baseline_subprocess(iters, timeout_s=240):
@@ -1063,6 +1113,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     sampler.__exit__()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     if trace:
         print('losses per step:', ' '.join('%d:%.4g/%.4g' % (i, float(t['loss_G']), float(t['loss_D']))
                                            for i, t in enumerate(trace)), file=sys.stderr)

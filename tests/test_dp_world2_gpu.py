@@ -14,8 +14,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two GPUs')
 def test_train_step_gradient_exchange_world2():
+    n = torch.cuda.device_count()
+    if n < 2:
+        pytest.skip('needs 2 GPUs, found %d' % n)
     sock = socket.socket()
     sock.bind(('127.0.0.1', 0))
     port = sock.getsockname()[1]

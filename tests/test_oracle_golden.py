@@ -159,8 +159,19 @@ def _train(golden, tag, n_groups, n_blocks, batch, lr_side, scale, iters):
     for k in ['conv1.0.weight', 'res_groups.0.RG.0.conv2.bias', 'GAB_UP.sa.gamma', 'GAB_UP.upsampling.0.weight',
               'conv3.0.weight']:
         _check(k, O.digest(gs[k])[:64], g['G_after__' + k.replace('.', '__')], rtol=1e-3, atol=2e-5)
-    for k in ['model.0.weight', 'model.3.weight', 'model.3.running_mean', 'model.25.weight']:
+    for k in ['model.0.weight', 'model.3.weight', 'model.25.weight']:
         _check(k, O.digest(ds[k])[:64], g['D_after__' + k.replace('.', '__')], rtol=1e-3, atol=2e-5)
+    # model.3.running_mean: BatchNorm model.3 cancels the bias of conv model.2 in front of it, so that bias's gradient is
+    # roundoff whose sign follows the CPU's summation order (thread count, the vendor's BLAS / oneDNN kernels), and Adam's
+    # first step turns it into +-lr.  The four training-mode D forwards of iteration 2 carry the bias into the running mean
+    # with weight 1 - 0.9^4, so per channel the recorded value and this host's differ by 0 or +-2 lr (1 - 0.9^4) = 1.3755e-4
+    # on top of the same tolerance as the other tensors.
+    got = O.digest(ds['model.3.running_mean'])[:64].astype(np.float64)
+    want = g['D_after__model__3__running_mean'].astype(np.float64)
+    q = 2 * 2e-4 * (1 - 0.9 ** 4)
+    resid = np.min(np.abs((got - want)[None, :] - np.array([[-q], [0.0], [q]])), axis=0)
+    bound = 2e-5 * max(1.0, float(np.abs(want).max())) + 1e-3 * np.abs(want)
+    assert (resid <= bound).all(), ('model.3.running_mean', resid.max(), int((resid > bound).sum()))
 
 
 def test_train_two_iterations_small(golden):

@@ -84,7 +84,12 @@ def _check_step_weights(G, D, g, rtol, adam_bound=None):
             t = sd[key[3:].replace('__', '.')].float().cpu()
             d = O.digest(t)
             if adam_bound is None:
-                assert np.abs(d - g[key]).max() <= rtol * max(1.0, np.abs(g[key]).max()), key
+                n = d.size - 2 if t.numel() > 4096 else d.size
+                tol = rtol * max(1.0, np.abs(g[key]).max())
+                assert np.abs(d[:n] - g[key][:n]).max() <= tol, key
+                # the digest's [sum, l2] tail adds up every element, those whose gradient sign is roundoff included: Adam moves
+                # each of them by +-lr per step on any two CPUs, so the tail is held to one such element's 2 * lr * iterations
+                assert np.abs(d[n:] - g[key][n:]).max(initial=0.0) <= max(tol, 2 * 2e-4 * 2), key
             else:
                 n = d.size - 2 if t.numel() > 4096 else d.size            # drop the digest's [sum, l2] tail
                 dev = np.abs(d[:n] - g[key][:n])
@@ -102,7 +107,13 @@ def test_oracle_training_iterations_match_reference_vectors():
     O.det_init_(D, prefix='SD.')
     O.det_init_(Fx, prefix='V.')
     rows = _run_steps(G, D, Fx, S.train_step)
-    assert np.abs(rows - g['scalars']).max() < 2e-6, np.abs(rows - g['scalars']).max()
+    dev = np.abs(rows - g['scalars'])
+    # iteration 1 runs on the recorded initial weights: the reference's arithmetic to roundoff.  Iteration 2 runs on weights
+    # after one Adam step, which turns every gradient whose sign is roundoff into a +-lr step whose direction follows the CPU's
+    # summation order (thread count, the vendor's BLAS / oneDNN kernels): measured up to 7e-7 across 1-16 threads on the
+    # recording CPU, 2.3e-6 on an AMD EPYC host.
+    assert dev[0].max() < 2e-6, dev
+    assert dev[1].max() < 5e-6, dev
     _check_step_weights(G, D, g, 1e-5)
 
 

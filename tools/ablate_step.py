@@ -3,7 +3,6 @@ return at once: outputs stay uninitialised, so results are garbage -- timing onl
 bounds what any optimisation of that family can gain.  Usage: python tools/ablate_step.py [family ...]   (default: all)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 import bench
 from sradsgan_amd import _hip

@@ -1,7 +1,6 @@
 """Where the host spends its time in one eager training step (cProfile over 6 steps at the bench shape)."""
 import cProfile, os, pstats, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 import bench
 from sradsgan_amd.train_step import TrainStep

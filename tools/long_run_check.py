@@ -4,7 +4,6 @@ trajectories and final weights -- a race between streams (an event ring wrapping
 wrong producer) would show up as a difference somewhere along 150 steps."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 import bench
 from sradsgan_amd.train_step import TrainStep
