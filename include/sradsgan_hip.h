@@ -53,7 +53,9 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *        added (no existing entry point changed).
  * ABI 6-9: see the notes at the entry points they added.
  * ABI 10: srhip_attn_tail_bwd_g REMOVED (nothing else changed).
- * ABI 11: srhip_cat_channels / srhip_split_channels added. */
+ * ABI 11: srhip_cat_channels / srhip_split_channels added.
+ * ABI 12: DSSR's average-pool channel attention (srhip_ca_*), the upsampler fold passes (srhip_add_bcast_scaled,
+ *         srhip_batch_sum_scaled) and srhip_mse_mean_* added (no existing entry point changed). */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -252,6 +254,35 @@ int srhip_lrelu_bwd_bits(const float* dy, const float* y, void* mask, float* dx,
  * the stratified dense-sampling bus of GeneratorResNet.forward (sradsgan.py:455-460: `bus = bus + out` after every residual
  * group) in one pass, same summation order as the chained torch adds it replaces.                                            */
 int srhip_sum_n(const float* const* srcs, int n, float* out, long count, void* stream);
+/* ABI 12 -- DSSR's wide-activation block tail (model/dssr.py:69-104): out = s * u + x with s[n,c] = sigmoid(fc2 relu(fc1 mean_hw u)),
+ * the average-pool-only channel attention (bias-free 64 -> hidden -> 64 MLP, hidden <= 16) followed by the block's `out += x`.
+ * u, x, g, du, out: NHWC with C == 64 dense channels, 16-byte aligned; avg, s, dmean: [n][64]; hid: [n][hidden].
+ *   srhip_ca_pool_sum    : psum[n][srhip_ca_segments()][64] = per-segment channel sums of u (when no conv epilogue left them:
+ *                          the sum section of srhip_conv2d_fwd_pool's partials has the same layout, with its own nseg)
+ *   srhip_ca_mlp_fwd     : avg = sum of the nseg partials / hw, hid = relu(fc1 avg), s = sigmoid(fc2 hid), one block per image
+ *   srhip_ca_scale_res   : out = s * u + x (s * u is never written on its own)
+ *   srhip_ca_bwd_partial : part[n][srhip_ca_segments()][64] = per-segment sums of g * u (fixed order, no atomics)
+ *   srhip_ca_mlp_bwd     : the MLP and sigmoid backward (one block per image, then one pass for the weights): dfc1 [hidden][64],
+ *                          dfc2 [64][hidden] (written, summed over the images in order) and dmean = d(loss)/d(mean_hw u) / hw;
+ *                          workspace >= srhip_ca_mlp_bwd_workspace(n, hidden)
+ *   srhip_ca_bwd_du      : du = s * g + dmean (dx = g is the caller's)
+ * All results are bit-identical from run to run.
+ * The upsampler fold (model/dssr.py:170-177: sum_i UP(x_i) = UP(sum_i x_i) + G UP(0), UP affine):
+ *   srhip_add_bcast_scaled : out[b][i] = a[b][i] + scale * bcast[i], per_image % 4 == 0
+ *   srhip_batch_sum_scaled : out[i] = scale * sum_b g[b][i], images in order (its backward)                                    */
+int srhip_ca_segments(void);
+int srhip_ca_pool_sum(const float* u, float* psum, int n, int hw, int c, void* stream);
+int srhip_ca_mlp_fwd(const float* psum, int nseg, const float* fc1, const float* fc2, float* avg, float* hid, float* s, int n, int hw,
+                     int c, int hidden, void* stream);
+int srhip_ca_scale_res(const float* u, const float* s, const float* x, float* out, int n, int hw, int c, void* stream);
+int srhip_ca_bwd_partial(const float* g, const float* u, float* part, int n, int hw, int c, void* stream);
+size_t srhip_ca_mlp_bwd_workspace(int n, int hidden);
+int srhip_ca_mlp_bwd(const float* part, const float* avg, const float* hid, const float* s, const float* fc1, const float* fc2,
+                     float* dmean, float* dfc1, float* dfc2, void* workspace, size_t workspace_bytes, int n, int hw, int c, int hidden,
+                     void* stream);
+int srhip_ca_bwd_du(const float* g, const float* s, const float* dmean, float* du, int n, int hw, int c, void* stream);
+int srhip_add_bcast_scaled(const float* a, const float* b, float scale, float* out, int n, long per_image, void* stream);
+int srhip_batch_sum_scaled(const float* g, float scale, float* out, int n, long per_image, void* stream);
 /* ABI 11: torch.cat(dim = 1) of n = 2..8 NHWC tensors with `rows` pixel rows each and chans[k] channels (multiples of 4, 16-byte aligned
  * tensors) -- the multi-scale block's three branches, sradsgan.py:340-344 -- and its backward: the wide tensor split back into n dense ones. */
 int srhip_cat_channels(const float* const* srcs, const int* chans, int n, float* out, long rows, void* stream);
@@ -406,6 +437,12 @@ size_t srhip_reduce_workspace(void);
 int srhip_l1_mean_fwd(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, long count,
                       void* stream);
 int srhip_l1_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long count, void* stream);
+/* ABI 12 -- mse_mean: nn.MSELoss() (DSSR, model/dssr.py:266-269 with loss_Lp_norm='L2'): out = mean (a - b)^2;
+ *           bwd: da = 2 (a - b) * gout / count, db = -da when db != NULL.  Any count (the tail that is not a multiple of 4 is
+ *           read with scalar loads). */
+int srhip_mse_mean_fwd(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, long count,
+                       void* stream);
+int srhip_mse_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long count, void* stream);
 int srhip_mean_fwd(const float* x, float* out, void* workspace, size_t workspace_bytes, long count, void* stream);
 int srhip_mean_bwd(const float* gout, float* dx, long count, void* stream);
 int srhip_gp_norm_penalty_fwd(const float* grads, float* out, void* workspace, size_t workspace_bytes, long npix, int c,

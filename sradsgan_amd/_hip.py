@@ -95,6 +95,8 @@ SIGNATURES = {
     'srhip_reduce_workspace': (_sz, []),
     'srhip_l1_mean_fwd': (_i, [_vp] * 4 + [_sz, _l, _vp]),
     'srhip_l1_mean_bwd': (_i, [_vp] * 5 + [_l, _vp]),
+    'srhip_mse_mean_fwd': (_i, [_vp] * 4 + [_sz, _l, _vp]),
+    'srhip_mse_mean_bwd': (_i, [_vp] * 5 + [_l, _vp]),
     'srhip_mean_fwd': (_i, [_vp] * 3 + [_sz, _l, _vp]),
     'srhip_mean_bwd': (_i, [_vp] * 2 + [_l, _vp]),
     'srhip_gp_norm_penalty_fwd': (_i, [_vp] * 3 + [_sz, _l, _i, _vp]),
@@ -120,6 +122,16 @@ SIGNATURES = {
     'srhip_attn_tail_fwd_pooled': (_i, [_vp, _vp, _sz, _i] + [_vp] * 10 + [_i] * 5 + [_vp]),
     'srhip_attn_tail_eval_pooled': (_i, [_vp, _vp, _vp, _sz, _i] + [_vp] * 6 + [_i] * 5 + [_vp]),
     'srhip_sum_n': (_i, [_vp, _i, _vp, _l, _vp]),
+    'srhip_ca_segments': (_i, []),
+    'srhip_ca_pool_sum': (_i, [_vp, _vp] + [_i] * 3 + [_vp]),
+    'srhip_ca_mlp_fwd': (_i, [_vp, _i] + [_vp] * 5 + [_i] * 4 + [_vp]),
+    'srhip_ca_scale_res': (_i, [_vp] * 4 + [_i] * 3 + [_vp]),
+    'srhip_ca_bwd_partial': (_i, [_vp] * 3 + [_i] * 3 + [_vp]),
+    'srhip_ca_mlp_bwd_workspace': (_sz, [_i, _i]),
+    'srhip_ca_mlp_bwd': (_i, [_vp] * 10 + [_sz] + [_i] * 4 + [_vp]),
+    'srhip_ca_bwd_du': (_i, [_vp] * 4 + [_i] * 3 + [_vp]),
+    'srhip_add_bcast_scaled': (_i, [_vp, _vp, _f, _vp, _i, _l, _vp]),
+    'srhip_batch_sum_scaled': (_i, [_vp, _f, _vp, _i, _l, _vp]),
     'srhip_cat_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_split_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_bn_train_bwd_acc': (_i, [_vp] * 12 + [_sz, _l, _i, _f, _i, _vp]),

@@ -1,4 +1,5 @@
-// Loss reductions of the training step (SRADSGAN/model/sradsgan.py): nn.L1Loss (:686, used :834, :838), the WGAN
+// Loss reductions of the training step (SRADSGAN/model/sradsgan.py): nn.L1Loss (:686, used :834, :838), nn.MSELoss (DSSR's
+// loss_Lp_norm='L2', model/dssr.py:266-269), the WGAN
 // critic means of GANLoss (:35-67, used :847, :876-878) and the gradient-penalty reduction (:630-637: per-pixel L2
 // norm over channels, (norm - 1)^2, mean).  Each is one pass over its input (HBM-bound, 16-byte loads where the
 // layout allows) into per-block partial sums, and one single-block pass that adds the partials in a fixed order:
@@ -29,6 +30,26 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
   }
   if (blockIdx.x == 0)
     for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) s += fabsf(a[i] - b[i]);
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// partial[block] = sum (a - b)^2 over a grid-stride range (nn.MSELoss, DSSR's loss_Lp_norm='L2')
+__global__ __launch_bounds__(256) void sq_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                         float* __restrict__ partial, long n) {
+  __shared__ float red[4];
+  const long n4 = n >> 2;
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 x = reinterpret_cast<const float4*>(a)[i], y = reinterpret_cast<const float4*>(b)[i];
+    const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
+    s += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  }
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+      const float d = a[i] - b[i];
+      s += d * d;
+    }
   s = block_sum_256(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
@@ -76,6 +97,18 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ a
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float d = a[i] - b[i];
     const float v = d > 0.f ? gs : (d < 0.f ? -gs : 0.f);
+    da[i] = v;
+    if (db) db[i] = -v;
+  }
+}
+
+// da = 2 (a - b) * gout / n; db = -da when asked for
+__global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                     const float* __restrict__ gout, float* __restrict__ da,
+                                                     float* __restrict__ db, long n, float inv_n) {
+  const float gs = 2.f * gout[0] * inv_n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float v = gs * (a[i] - b[i]);
     da[i] = v;
     if (db) db[i] = -v;
   }
@@ -140,6 +173,24 @@ int srhip_l1_mean_bwd(const float* a, const float* b, const float* gout, float* 
   hipLaunchKernelGGL(l1_bwd_kernel, dim3(ls_blocks(count)), dim3(256), 0, as_stream(stream), a, b, gout, da, db, count,
                      (float)(1.0 / (double)count));
   return check_launch("l1_mean_bwd");
+}
+
+int srhip_mse_mean_fwd(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, long count, void* stream) {
+  SRHIP_REQUIRE(count > 0, "mse_mean_fwd: empty input");
+  SRHIP_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 15) == 0, "mse_mean_fwd: inputs must be 16-byte aligned");
+  if (!ws_ok("mse_mean_fwd", workspace, workspace_bytes)) return SRHIP_ERR_WORKSPACE;
+  const int nb = ls_blocks(count / 4 + 1);
+  float* part = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(sq_partial_kernel, dim3(nb), dim3(256), 0, as_stream(stream), a, b, part, count);
+  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, as_stream(stream), part, nb, (float)(1.0 / (double)count), out);
+  return check_launch("mse_mean_fwd");
+}
+
+int srhip_mse_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long count, void* stream) {
+  SRHIP_REQUIRE(count > 0 && da != nullptr, "mse_mean_bwd: empty input / missing output");
+  hipLaunchKernelGGL(sq_bwd_kernel, dim3(ls_blocks(count)), dim3(256), 0, as_stream(stream), a, b, gout, da, db, count,
+                     (float)(1.0 / (double)count));
+  return check_launch("mse_mean_bwd");
 }
 
 int srhip_mean_fwd(const float* x, float* out, void* workspace, size_t workspace_bytes, long count, void* stream) {

@@ -2408,3 +2408,164 @@ class _GpPenalty(Function):
 def gp_penalty(grads):
     """sradsgan.py:630-637: L2 norm over the channel dim (per pixel), LS penalty, mean."""
     return _GpPenalty.apply(grads)
+
+
+class _MseMean(Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        _require_gpu(a, 'mse_mean')
+        a = nhwc(a) if a.dim() == 4 else a.contiguous()
+        b = b.contiguous(memory_format=CL) if (b.dim() == 4) else b.contiguous()
+        if a.shape != b.shape:
+            raise ValueError('mse_mean: shapes differ: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
+        lib = _hip.lib()
+        out = torch.empty((), device=a.device, dtype=torch.float32)
+        ws = _ws(lib.srhip_reduce_workspace(), a)
+        _hip.check(lib.srhip_mse_mean_fwd(_p(a), _p(b), _p(out), _p(ws), ws.numel() * 4, a.numel(), _stream()), 'mse_mean_fwd')
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad
+        da = torch.empty_like(a, memory_format=CL) if a.dim() == 4 else torch.empty_like(a)
+        db = (torch.empty_like(a, memory_format=CL) if a.dim() == 4 else torch.empty_like(a)) if need_b else None
+        _hip.check(_hip.lib().srhip_mse_mean_bwd(_p(a), _p(b), _p(gout.contiguous()), _p(da), _p(db), a.numel(), _stream()),
+                   'mse_mean_bwd')
+        return (da if need_a else None), db
+
+
+def mse_mean(a, b):
+    """nn.MSELoss() (DSSR's loss_Lp_norm='L2', model/dssr.py:266-269)."""
+    return _MseMean.apply(a, b)
+
+
+# --------------------------------------------------------------------------------------------- #
+# DSSR (model/dssr.py:69-177): average-pool channel attention + residual, and the upsampler fold
+# --------------------------------------------------------------------------------------------- #
+
+
+class _ConvPool(Function):
+    """y = conv3x3(x, w) + b (stride 1, pad 1, 64 output channels) that also leaves the channel pooling partials of y behind
+    (srhip_conv2d_fwd_pool).  Returns (y, pool buffer, segments per image); only y is differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        y, (pool, sec, nseg) = conv2d_fwd_pool_raw(x, w, b)
+        ctx.save_for_backward(x, w, b)
+        ctx.mark_non_differentiable(pool)
+        return y, pool, nseg
+
+    @staticmethod
+    def backward(ctx, dy, _dpool, _dnseg):
+        x, w, b = ctx.saved_tensors
+        skip = _skip_param_grads(w)
+        dx = _ConvDgrad.apply(dy, w, tuple(x.shape), 1, 1) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        want_b = b is not None and ctx.needs_input_grad[2] and not skip
+        if ctx.needs_input_grad[1] and not skip and _state.direct_grads and not torch.is_grad_enabled():
+            dw, db = wgrad_for_params(w, b, x, dy, 1, 1, want_b)
+        elif ctx.needs_input_grad[1] and not skip:
+            dw, db = _ConvWgrad.apply(x, dy, tuple(w.shape), 1, 1, want_b)
+        elif want_b:
+            db = _ColSum.apply(dy)
+        return dx, dw, db
+
+
+def conv2d_pool(x, weight, bias=None):
+    """conv2d(x, weight, bias, 1, 1) plus the channel sums of its output as (pool buffer, segments per image) when the conv's
+    epilogue can produce them (pool_epilogue_ok), else (y, None)."""
+    if pool_epilogue_ok(x, weight):
+        y, pool, nseg = _ConvPool.apply(x, weight, bias)
+        return y, (pool, nseg)
+    return conv2d(x, weight, bias, 1, 1), None
+
+
+class _CaResidual(Function):
+    """out = sigmoid(fc2 relu(fc1 mean_hw u)) * u + x: dssr.py:69-82 (CA with the average pool only) and the `out += x` of WAB
+    (:103).  Three launches forward (pooling pass unless the conv that produced u left its sums, MLP, scale + add), four
+    backward (g * u partials, per-image MLP backward, MLP weight gradients, du); deterministic."""
+
+    @staticmethod
+    def forward(ctx, u, x, fc1_w, fc2_w, pool=None):
+        _require_gpu(u, 'ca_residual')
+        u, x = nhwc(u), nhwc(x)
+        n, c, h, w = u.shape
+        if c != 64 or x.shape != u.shape:
+            raise ValueError('ca_residual: u and x must be [n, 64, h, w] of one shape, got %s / %s' % (tuple(u.shape), tuple(x.shape)))
+        lib = _hip.lib()
+        f32 = dict(device=u.device, dtype=torch.float32)
+        hid = fc1_w.shape[0]
+        if pool is None:
+            nseg = lib.srhip_ca_segments()
+            psum = torch.empty(n * nseg * c, **f32)
+            _hip.check(lib.srhip_ca_pool_sum(_p(u), _p(psum), n, h * w, c, _stream()), 'ca_pool_sum')
+        else:
+            psum, nseg = pool                        # the sum section leads the conv epilogue's [sum | max | arg] buffer
+        avg, s, hidden = torch.empty(n, c, **f32), torch.empty(n, c, **f32), torch.empty(n, hid, **f32)
+        fc1c, fc2c = fc1_w.detach().contiguous(), fc2_w.detach().contiguous()
+        _hip.check(lib.srhip_ca_mlp_fwd(_p(psum), nseg, _p(fc1c), _p(fc2c), _p(avg), _p(hidden), _p(s), n, h * w, c, hid, _stream()),
+                   'ca_mlp_fwd')
+        out = torch.empty_like(u, memory_format=CL)
+        _hip.check(lib.srhip_ca_scale_res(_p(u), _p(s), _p(x), _p(out), n, h * w, c, _stream()), 'ca_scale_res')
+        ctx.save_for_backward(u, fc1c, fc2c, avg, hidden, s)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        u, fc1c, fc2c, avg, hidden, s = ctx.saved_tensors
+        g = nhwc(g)
+        n, c, h, w = u.shape
+        lib = _hip.lib()
+        f32 = dict(device=u.device, dtype=torch.float32)
+        part = torch.empty(n * lib.srhip_ca_segments() * c, **f32)
+        _hip.check(lib.srhip_ca_bwd_partial(_p(g), _p(u), _p(part), n, h * w, c, _stream()), 'ca_bwd_partial')
+        dmean = torch.empty(n, c, **f32)
+        dfc1, dfc2 = torch.empty(fc1c.shape, **f32), torch.empty(fc2c.shape, **f32)
+        ws = _ws(lib.srhip_ca_mlp_bwd_workspace(n, fc1c.shape[0]), u)
+        _hip.check(lib.srhip_ca_mlp_bwd(_p(part), _p(avg), _p(hidden), _p(s), _p(fc1c), _p(fc2c), _p(dmean), _p(dfc1), _p(dfc2),
+                                        _p(ws), ws.numel() * 4, n, h * w, c, fc1c.shape[0], _stream()), 'ca_mlp_bwd')
+        du = torch.empty_like(u, memory_format=CL)
+        _hip.check(lib.srhip_ca_bwd_du(_p(g), _p(s), _p(dmean), _p(du), n, h * w, c, _stream()), 'ca_bwd_du')
+        need = ctx.needs_input_grad
+        return (du if need[0] else None, _passed_through(g) if need[1] else None, dfc1 if need[2] else None,
+                dfc2 if need[3] else None, None)
+
+
+def ca_residual(u, x, fc1_w, fc2_w, pool=None):
+    """sigmoid(fc2(relu(fc1(avgpool u)))) * u + x (dssr.py:69-82, 103) for 64-channel u.  pool: (buffer, segments per image) from
+    conv2d_pool, whose leading section holds the channel sums of u; None runs a pooling pass."""
+    return _CaResidual.apply(u, x, fc1_w, fc2_w, pool)
+
+
+class _AddBcastScaled(Function):
+    """out = a + scale * b, b of batch 1 broadcast over a's batch: UP(S) + G * UP(0) of the DSSR upsampler fold."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale):
+        _require_gpu(a, 'add_bcast_scaled')
+        a, b = nhwc(a), nhwc(b)
+        if b.shape[0] != 1 or b.shape[1:] != a.shape[1:]:
+            raise ValueError('add_bcast_scaled: b must have the shape of a with batch 1, got %s / %s' % (tuple(a.shape), tuple(b.shape)))
+        out = torch.empty_like(a, memory_format=CL)
+        _hip.check(_hip.lib().srhip_add_bcast_scaled(_p(a), _p(b), float(scale), _p(out), a.shape[0], b.numel(), _stream()),
+                   'add_bcast_scaled')
+        ctx.scale, ctx.n = float(scale), a.shape[0]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        g = nhwc(g)
+        db = None
+        if ctx.needs_input_grad[1]:
+            db = empty_nhwc(1, *g.shape[1:], like=g)
+            _hip.check(_hip.lib().srhip_batch_sum_scaled(_p(g), ctx.scale, _p(db), ctx.n, db.numel(), _stream()), 'batch_sum_scaled')
+        return g, db, None
+
+
+def add_bcast_scaled(a, b, scale):
+    """a + scale * b with b [1, C, H, W] broadcast over a's batch (NHWC, C*H*W % 4 == 0)."""
+    return _AddBcastScaled.apply(a, b, scale)
