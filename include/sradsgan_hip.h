@@ -55,7 +55,9 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  * ABI 10: srhip_attn_tail_bwd_g REMOVED (nothing else changed).
  * ABI 11: srhip_cat_channels / srhip_split_channels added.
  * ABI 12: DSSR's average-pool channel attention (srhip_ca_*), the upsampler fold passes (srhip_add_bcast_scaled,
- *         srhip_batch_sum_scaled) and srhip_mse_mean_* added (no existing entry point changed). */
+ *         srhip_batch_sum_scaled) and srhip_mse_mean_* added (no existing entry point changed).
+ * ABI 13: NDSRGAN's passes (srhip_scaled_res_fwd / _bwd, srhip_lrelu_bwd_strided, srhip_upsample_nearest_fwd / _bwd) and
+ *         srhip_smooth_l1_mean_* added (no existing entry point changed). */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -283,6 +285,27 @@ int srhip_ca_mlp_bwd(const float* part, const float* avg, const float* hid, cons
 int srhip_ca_bwd_du(const float* g, const float* s, const float* dmean, float* du, int n, int hw, int c, void* stream);
 int srhip_add_bcast_scaled(const float* a, const float* b, float scale, float* out, int n, long per_image, void* stream);
 int srhip_batch_sum_scaled(const float* g, float scale, float* out, int n, long per_image, void* stream);
+/* ABI 13 -- NDSRGAN (model/ndsrgan.py:57-211).  Rows are pixels; every operand has its own row stride (floats, multiple of 4, >= ch),
+ * all pointers 16-byte aligned, ch % 4 == 0.  A dense block keeps its input and the four CL outputs in ONE [n, h, w, 192] buffer:
+ * CL j reads channels 0 : 64+32j (srhip_conv2d_fwd ldx = 192) and writes 64+32j : 96+32j (ldy = 192), and the passes below write a
+ * block's result straight into channels 0:64 of the next block's buffer -- no torch.cat, no copy.
+ *   srhip_scaled_res_fwd   : y = r + alpha * c (c NULL: y = r), z = s + beta * y; y or z NULL: not written.  DenseBlock / DCRDB end
+ *                            in `r + conv * 0.2` (:75, :92) and the trunk forms running sums `s + 0.2 * y` (:89-91, :121-146), in
+ *                            the reference's fp32 operation order.
+ *   srhip_scaled_res_bwd   : dc = ka * dz (dc non-NULL); dr[0:ch] = kb * dz + kc * e (e optional), dr[ch:width] = 0 (dr non-NULL):
+ *                            the gradient at the conv and the initial gradient of a dense-block buffer in one pass.
+ *   srhip_lrelu_bwd_strided: dx = dy * (y > 0 ? 1 : slope) over ch channels (in place when dx == dy): the CL's LeakyReLU(0.2)
+ *                            backward, the mask from the post-activation values in the buffer.
+ *   srhip_upsample_nearest_fwd / _bwd: nn.UpsamplingNearest2d(r), r in {2, 3}, NHWC [n, h, w, c] <-> [n, r h, r w, c]; the backward
+ *                            sums each r x r block in a fixed order (no atomics).                                                  */
+int srhip_scaled_res_fwd(const float* r, int ldr, const float* c, int ldc, const float* s, int lds, float alpha, float beta, float* y,
+                         int ldy, float* z, int ldz, long rows, int ch, void* stream);
+int srhip_scaled_res_bwd(const float* dz, int ldz, const float* e, int lde, float ka, float kb, float kc, float* dc, int ldc, float* dr,
+                         int ldr, int width, long rows, int ch, void* stream);
+int srhip_lrelu_bwd_strided(const float* dy, int ldg, const float* y, int ldy, float* dx, int ldx, float slope, long rows, int ch,
+                            void* stream);
+int srhip_upsample_nearest_fwd(const float* x, float* y, int n, int h, int w, int c, int r, void* stream);
+int srhip_upsample_nearest_bwd(const float* dy, float* dx, int n, int h, int w, int c, int r, void* stream);
 /* ABI 11: torch.cat(dim = 1) of n = 2..8 NHWC tensors with `rows` pixel rows each and chans[k] channels (multiples of 4, 16-byte aligned
  * tensors) -- the multi-scale block's three branches, sradsgan.py:340-344 -- and its backward: the wide tensor split back into n dense ones. */
 int srhip_cat_channels(const float* const* srcs, const int* chans, int n, float* out, long rows, void* stream);
@@ -443,6 +466,13 @@ int srhip_l1_mean_bwd(const float* a, const float* b, const float* gout, float* 
 int srhip_mse_mean_fwd(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, long count,
                        void* stream);
 int srhip_mse_mean_bwd(const float* a, const float* b, const float* gout, float* da, float* db, long count, void* stream);
+/* ABI 13 -- smooth_l1_mean: nn.SmoothL1Loss() (beta = 1, mean; NDSRGAN, model/ndsrgan.py:325-351): out = mean sl1(a - t) with
+ *           t = b[i], or the scalar `target` when b == NULL (D's valid / fake targets, no ones tensor); sl1(d) = |d| < 1 ? d^2 / 2 :
+ *           |d| - 1/2.  bwd: da = clamp(a - t, -1, 1) * gout / count, db = -da when db != NULL (needs b). */
+int srhip_smooth_l1_mean_fwd(const float* a, const float* b, float target, float* out, void* workspace, size_t workspace_bytes,
+                             long count, void* stream);
+int srhip_smooth_l1_mean_bwd(const float* a, const float* b, float target, const float* gout, float* da, float* db, long count,
+                             void* stream);
 int srhip_mean_fwd(const float* x, float* out, void* workspace, size_t workspace_bytes, long count, void* stream);
 int srhip_mean_bwd(const float* gout, float* dx, long count, void* stream);
 int srhip_gp_norm_penalty_fwd(const float* grads, float* out, void* workspace, size_t workspace_bytes, long npix, int c,

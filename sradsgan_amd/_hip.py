@@ -97,6 +97,8 @@ SIGNATURES = {
     'srhip_l1_mean_bwd': (_i, [_vp] * 5 + [_l, _vp]),
     'srhip_mse_mean_fwd': (_i, [_vp] * 4 + [_sz, _l, _vp]),
     'srhip_mse_mean_bwd': (_i, [_vp] * 5 + [_l, _vp]),
+    'srhip_smooth_l1_mean_fwd': (_i, [_vp, _vp, _f, _vp, _vp, _sz, _l, _vp]),
+    'srhip_smooth_l1_mean_bwd': (_i, [_vp, _vp, _f] + [_vp] * 3 + [_l, _vp]),
     'srhip_mean_fwd': (_i, [_vp] * 3 + [_sz, _l, _vp]),
     'srhip_mean_bwd': (_i, [_vp] * 2 + [_l, _vp]),
     'srhip_gp_norm_penalty_fwd': (_i, [_vp] * 3 + [_sz, _l, _i, _vp]),
@@ -132,6 +134,11 @@ SIGNATURES = {
     'srhip_ca_bwd_du': (_i, [_vp] * 4 + [_i] * 3 + [_vp]),
     'srhip_add_bcast_scaled': (_i, [_vp, _vp, _f, _vp, _i, _l, _vp]),
     'srhip_batch_sum_scaled': (_i, [_vp, _f, _vp, _i, _l, _vp]),
+    'srhip_scaled_res_fwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _i, _vp, _i, _l, _i, _vp]),
+    'srhip_scaled_res_bwd': (_i, [_vp, _i, _vp, _i, _f, _f, _f, _vp, _i, _vp, _i, _i, _l, _i, _vp]),
+    'srhip_lrelu_bwd_strided': (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _l, _i, _vp]),
+    'srhip_upsample_nearest_fwd': (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
+    'srhip_upsample_nearest_bwd': (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
     'srhip_cat_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_split_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_bn_train_bwd_acc': (_i, [_vp] * 12 + [_sz, _l, _i, _f, _i, _vp]),

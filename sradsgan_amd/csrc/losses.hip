@@ -1,5 +1,5 @@
 // Loss reductions of the training step (SRADSGAN/model/sradsgan.py): nn.L1Loss (:686, used :834, :838), nn.MSELoss (DSSR's
-// loss_Lp_norm='L2', model/dssr.py:266-269), the WGAN
+// loss_Lp_norm='L2', model/dssr.py:266-269), nn.SmoothL1Loss (NDSRGAN, model/ndsrgan.py:325-351), the WGAN
 // critic means of GANLoss (:35-67, used :847, :876-878) and the gradient-penalty reduction (:630-637: per-pixel L2
 // norm over channels, (norm - 1)^2, mean).  Each is one pass over its input (HBM-bound, 16-byte loads where the
 // layout allows) into per-block partial sums, and one single-block pass that adds the partials in a fixed order:
@@ -50,6 +50,29 @@ __global__ __launch_bounds__(256) void sq_partial_kernel(const float* __restrict
       const float d = a[i] - b[i];
       s += d * d;
     }
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// SmoothL1 with beta = 1 (torch's smooth_l1_loss): |d| < 1 ? 0.5 d^2 : |d| - 0.5
+__device__ __forceinline__ float smooth_l1(float d) {
+  const float z = fabsf(d);
+  return z < 1.f ? 0.5f * z * z : z - 0.5f;
+}
+
+// partial[block] = sum smooth_l1(a - t), t = b[i] or the scalar tgt when b == NULL (NDSRGAN's valid / fake targets)
+__global__ __launch_bounds__(256) void smooth_l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, float tgt,
+                                                                float* __restrict__ partial, long n) {
+  __shared__ float red[4];
+  const long n4 = n >> 2;
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 x = reinterpret_cast<const float4*>(a)[i];
+    const float4 y = b ? reinterpret_cast<const float4*>(b)[i] : make_float4(tgt, tgt, tgt, tgt);
+    s += (smooth_l1(x.x - y.x) + smooth_l1(x.y - y.y)) + (smooth_l1(x.z - y.z) + smooth_l1(x.w - y.w));
+  }
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) s += smooth_l1(a[i] - (b ? b[i] : tgt));
   s = block_sum_256(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
@@ -109,6 +132,19 @@ __global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ a
   const float gs = 2.f * gout[0] * inv_n;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float v = gs * (a[i] - b[i]);
+    da[i] = v;
+    if (db) db[i] = -v;
+  }
+}
+
+// da = clamp(a - t, -1, 1) * gout / n; db = -da when asked for (t = b[i], or tgt when b == NULL)
+__global__ __launch_bounds__(256) void smooth_l1_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float tgt,
+                                                            const float* __restrict__ gout, float* __restrict__ da,
+                                                            float* __restrict__ db, long n, float inv_n) {
+  const float gs = gout[0] * inv_n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float d = a[i] - (b ? b[i] : tgt);
+    const float v = (d <= -1.f ? -1.f : (d >= 1.f ? 1.f : d)) * gs;
     da[i] = v;
     if (db) db[i] = -v;
   }
@@ -191,6 +227,26 @@ int srhip_mse_mean_bwd(const float* a, const float* b, const float* gout, float*
   hipLaunchKernelGGL(sq_bwd_kernel, dim3(ls_blocks(count)), dim3(256), 0, as_stream(stream), a, b, gout, da, db, count,
                      (float)(1.0 / (double)count));
   return check_launch("mse_mean_bwd");
+}
+
+int srhip_smooth_l1_mean_fwd(const float* a, const float* b, float target, float* out, void* workspace, size_t workspace_bytes,
+                             long count, void* stream) {
+  SRHIP_REQUIRE(count > 0, "smooth_l1_mean_fwd: empty input");
+  SRHIP_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 15) == 0, "smooth_l1_mean_fwd: inputs must be 16-byte aligned");
+  if (!ws_ok("smooth_l1_mean_fwd", workspace, workspace_bytes)) return SRHIP_ERR_WORKSPACE;
+  const int nb = ls_blocks(count / 4 + 1);
+  float* part = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(smooth_l1_partial_kernel, dim3(nb), dim3(256), 0, as_stream(stream), a, b, target, part, count);
+  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, as_stream(stream), part, nb, (float)(1.0 / (double)count), out);
+  return check_launch("smooth_l1_mean_fwd");
+}
+
+int srhip_smooth_l1_mean_bwd(const float* a, const float* b, float target, const float* gout, float* da, float* db, long count,
+                             void* stream) {
+  SRHIP_REQUIRE(count > 0 && da != nullptr && (b != nullptr || db == nullptr), "smooth_l1_mean_bwd: empty input / missing output");
+  hipLaunchKernelGGL(smooth_l1_bwd_kernel, dim3(ls_blocks(count)), dim3(256), 0, as_stream(stream), a, b, target, gout, da, db, count,
+                     (float)(1.0 / (double)count));
+  return check_launch("smooth_l1_mean_bwd");
 }
 
 int srhip_mean_fwd(const float* x, float* out, void* workspace, size_t workspace_bytes, long count, void* stream) {

@@ -2569,3 +2569,388 @@ class _AddBcastScaled(Function):
 def add_bcast_scaled(a, b, scale):
     """a + scale * b with b [1, C, H, W] broadcast over a's batch (NHWC, C*H*W % 4 == 0)."""
     return _AddBcastScaled.apply(a, b, scale)
+
+
+# --------------------------------------------------------------------------------------------- #
+# NDSRGAN (model/ndsrgan.py:57-211): concat-free dense blocks, scaled residuals with running trunk sums, nearest upsampling,
+# SmoothL1
+# --------------------------------------------------------------------------------------------- #
+
+
+DENSE_NF, DENSE_NC, DENSE_W = 64, 32, 192          # block channels, growth per CL, width of a dense-block buffer (64 + 4 * 32)
+RES_SCALE = 0.2                                    # `x * 0.2` of the residuals and running sums
+LRELU_SLOPE = 0.2                                  # nn.LeakyReLU(0.2) of the CLs
+
+
+def _rowld(t):
+    """(t, row stride) for a logical NCHW tensor whose memory is NHWC pixel rows of stride ld >= C (a channel slice of a wider NHWC
+    buffer, or dense channels-last); anything else is made dense channels-last first."""
+    n, c, h, w = t.shape
+    st = t.stride()
+    ld = st[3]
+    if (st[1] == 1 and ld >= c and ld % 4 == 0 and st[2] == w * ld and (n == 1 or st[0] == h * w * ld)
+            and t.data_ptr() % 16 == 0):
+        return t, ld
+    return nhwc(t), c
+
+
+def _dense_buffer(n, h, w, like):
+    return empty_nhwc(n, DENSE_W, h, w, like)
+
+
+def conv2d_fwd_ld(x, ldx, w, b, y, ldy, n, h, wd, slope=None):
+    """stride-1 'same' conv reading cin channels of rows of stride ldx and writing cout channels into rows of stride ldy (bias,
+    optional fused LeakyReLU): a CL of a dense block reads a channel prefix of its buffer and writes its own slice of it."""
+    cout, cin, kh, kw = w.shape
+    flags = (EPI_BIAS if b is not None else 0) | (EPI_LRELU if slope is not None else 0)
+    bias = b.detach().contiguous() if b is not None else None
+    _hip.check(_hip.lib().srhip_conv2d_fwd(_p(x), _p(packed_weight(w, 0)), _p(bias), None, None, None, _p(y), n, h, wd, cin, cout, kh,
+                                           kw, 1, kh // 2, ldx, ldy, 0, float(slope or 0.0), flags, _stream()), 'conv2d_fwd (strided)')
+
+
+def conv2d_dgrad_ld(dy, ldy, w, dx, ldx, n, h, wd, accumulate):
+    """dx (rows of stride ldx, cin channels) = / += conv_transpose(dy, w) for a stride-1 'same' conv, dy rows of stride ldy."""
+    cout, cin, kh, kw = w.shape
+    _hip.check(_hip.lib().srhip_conv2d_dgrad(_p(dy), _p(packed_weight(w, 1)), _p(dx), None, None, 0.0, n, h, wd, cin, cout, kh, kw, 1,
+                                             kh // 2, ldy, ldx, cin, int(accumulate), _stream()), 'conv2d_dgrad (strided)')
+
+
+def conv2d_wgrad_ld(x, ldx, dy, ldy, w_shape, n, h, wd, with_bias=True):
+    """(dw, db) of a stride-1 'same' conv from x (cin channels of rows of stride ldx) and dy (rows of stride ldy)."""
+    cout, cin, kh, kw = w_shape
+    lib = _hip.lib()
+    nbytes = lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, 1, kh // 2)
+    ws = torch.empty((max(nbytes, 4) + 3) // 4, device=x.device, dtype=torch.float32)
+    dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x.device, dtype=torch.float32) if with_bias else None
+    _hip.check(lib.srhip_conv2d_wgrad(_p(x), _p(dy), _p(dw), _p(db), None, None, 0, _p(ws), ws.numel() * 4, n, h, wd, cin, cout, kh, kw,
+                                      1, kh // 2, ldx, ldy, _stream()), 'conv2d_wgrad (strided)')
+    return dw, db
+
+
+def scaled_res_raw(r, ldr, c, ldc, s, lds, alpha, beta, y, ldy, z, ldz, rows, ch=DENSE_NF):
+    """y = r + alpha * c, z = s + beta * y on raw rows (srhip_scaled_res_fwd); any of c, y, z may be None (see the header)."""
+    _hip.check(_hip.lib().srhip_scaled_res_fwd(_p(r), ldr, _p(c), ldc, _p(s), lds, float(alpha), float(beta), _p(y), ldy, _p(z), ldz,
+                                               rows, ch, _stream()), 'scaled_res_fwd')
+
+
+def scaled_res_bwd_raw(dz, ldz, e, lde, ka, kb, kc, dc, ldc, dr, ldr, width, rows, ch=DENSE_NF):
+    """dc = ka dz; dr[0:ch] = kb dz + kc e, dr[ch:width] = 0 (srhip_scaled_res_bwd)."""
+    _hip.check(_hip.lib().srhip_scaled_res_bwd(_p(dz), ldz, _p(e), lde, float(ka), float(kb), float(kc), _p(dc), ldc, _p(dr), ldr,
+                                               width, rows, ch, _stream()), 'scaled_res_bwd')
+
+
+def lrelu_bwd_strided_raw(dy, ldg, y, ldy, dx, ldx, slope, rows, ch):
+    _hip.check(_hip.lib().srhip_lrelu_bwd_strided(_p(dy), ldg, _p(y), ldy, _p(dx), ldx, float(slope), rows, ch, _stream()),
+               'lrelu_bwd_strided')
+
+
+def _dense_fwd(buf, wb, n, h, w, slope):
+    """The four CLs of a dense block inside its buffer (channels 0:64 hold the block input), then conv5 over all 192 channels.
+    Returns conv5's output (dense, bias included)."""
+    for j in range(4):
+        off = DENSE_NF + DENSE_NC * j
+        conv2d_fwd_ld(buf, DENSE_W, wb[2 * j], wb[2 * j + 1], buf[:, off:], DENSE_W, n, h, w, slope)
+    c5 = empty_nhwc(n, DENSE_NF, h, w, buf)
+    conv2d_fwd_ld(buf, DENSE_W, wb[8], wb[9], c5, DENSE_NF, n, h, w)
+    return c5
+
+
+def _dense_bwd(buf, wb, dz, ldz, e, lde, ka, kb, kc, n, h, w, slope, grads):
+    """Backward of one dense block whose result is r + alpha conv5(buf) (or a running sum of it): dz the gradient at the result, ka /
+    kb the factors it reaches conv5 / the block input with, e (optional) one more gradient of the block input added with factor kc.
+    Appends the 10 parameter gradients (CL weights / biases in order, conv5's last) to `grads`; returns the gradient buffer, whose
+    channels 0:64 are the block input's gradient."""
+    rows = n * h * w
+    dbuf = _dense_buffer(n, h, w, buf)
+    dc5 = empty_nhwc(n, DENSE_NF, h, w, buf)
+    scaled_res_bwd_raw(dz, ldz, e, lde, ka, kb, kc, dc5, DENSE_NF, dbuf, DENSE_W, DENSE_W, rows)
+    g = [None] * 10
+    g[8], g[9] = conv2d_wgrad_ld(buf, DENSE_W, dc5, DENSE_NF, tuple(wb[8].shape), n, h, w)
+    conv2d_dgrad_ld(dc5, DENSE_NF, wb[8], dbuf, DENSE_W, n, h, w, accumulate=True)
+    for j in range(3, -1, -1):
+        off = DENSE_NF + DENSE_NC * j
+        gs = dbuf[:, off:]
+        # every consumer of CL j's output (later CLs, conv5) has added its share: apply the LeakyReLU backward in place
+        lrelu_bwd_strided_raw(gs, DENSE_W, buf[:, off:], DENSE_W, gs, DENSE_W, slope, rows, DENSE_NC)
+        g[2 * j], g[2 * j + 1] = conv2d_wgrad_ld(buf, DENSE_W, gs, DENSE_W, tuple(wb[2 * j].shape), n, h, w)
+        conv2d_dgrad_ld(gs, DENSE_W, wb[2 * j], dbuf, DENSE_W, n, h, w, accumulate=True)
+    grads.extend(g)
+    return dbuf
+
+
+class _DenseStats:
+    fills = 0              # block inputs copied into a new dense buffer by _adopt_or_fill (the generator's forward makes none)
+
+
+dense_stats = _DenseStats()
+
+
+def _adopt_or_fill(x, ldx, n, h, w):
+    """The dense buffer whose channels 0:64 hold x: x's own buffer when the op that produced x wrote it there (its `_srhip_dense_buf`
+    tag), else a new buffer that x is copied into (one pass, counted in dense_stats.fills)."""
+    buf = getattr(x, '_srhip_dense_buf', None)
+    if buf is not None and ldx == DENSE_W and buf.data_ptr() == x.data_ptr() and buf.shape[0] == n and tuple(buf.shape[2:]) == (h, w):
+        return buf
+    dense_stats.fills += 1
+    buf = _dense_buffer(n, h, w, x)
+    scaled_res_raw(x, ldx, None, 0, None, 0, 0.0, 0.0, buf, DENSE_W, None, 0, n * h * w)
+    return buf
+
+
+def _result_tensor(x, chain):
+    """output of a block: channels 0:64 of the NEXT block's dense buffer (chain), tagged so that block adopts the buffer; or dense."""
+    n, _, h, w = x.shape
+    if not chain:
+        return empty_nhwc(n, DENSE_NF, h, w, x), DENSE_NF
+    nxt = _dense_buffer(n, h, w, x)
+    out = nxt[:, :DENSE_NF]
+    out._srhip_dense_buf = nxt
+    return out, DENSE_W
+
+
+class _DenseBlock(Function):
+    """DenseBlock (ndsrgan.py:60-76) on its own: x + 0.2 * conv5(cat(x, CL1, ..., CL4)), the concatenation never formed."""
+
+    @staticmethod
+    def forward(ctx, x, *wb):
+        _require_gpu(x, 'dense_block')
+        x, ldx = _rowld(x)
+        n, _, h, w = x.shape
+        buf = _adopt_or_fill(x, ldx, n, h, w)
+        c5 = _dense_fwd(buf, wb, n, h, w, LRELU_SLOPE)
+        y = empty_nhwc(n, DENSE_NF, h, w, x)
+        scaled_res_raw(buf, DENSE_W, c5, DENSE_NF, None, 0, RES_SCALE, 0.0, y, DENSE_NF, None, 0, n * h * w)
+        ctx.save_for_backward(buf, *wb)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        buf, *wb = ctx.saved_tensors
+        dy, ld = _rowld(dy)
+        n, _, h, w = dy.shape
+        grads = []
+        dbuf = _dense_bwd(buf, wb, dy, ld, None, 0, RES_SCALE, 1.0, 0.0, n, h, w, LRELU_SLOPE, grads)
+        return (dbuf[:, :DENSE_NF],) + tuple(grads)
+
+
+def dense_block(x, weights_and_biases):
+    """ndsrgan.py:60-76 for nf = 64, nc = 32: weights_and_biases = [w1, b1, ..., w4, b4, w5, b5] (CLs, then the 192 -> 64 conv)."""
+    return _DenseBlock.apply(x, *weights_and_biases)
+
+
+class _DcrdbStep(Function):
+    """One step of DRRDBnet (ndsrgan.py:94-158): S = x + 0.2 * DCRDB(x) with DCRDB (:78-92) = three dense blocks on running sums
+    t1 = x + .2 o1, t2 = t1 + .2 o2, t3 = t2 + .2 o3 (the reference's left-to-right sums, same fp32 operations), o4 = conv(t3),
+    DCRDB(x) = o4 * .2 + x.  Each t_i lands in channels 0:64 of the next dense block's buffer, and S in the next step's when
+    `chain`.  Backward: per dense block one srhip_scaled_res_bwd pass (conv5's gradient and the buffer's initial gradient), conv5's
+    wgrad and accumulating dgrad, then per CL (last first) the strided LeakyReLU backward in place, wgrad and accumulating dgrad
+    into the buffer's channel prefix."""
+
+    @staticmethod
+    def forward(ctx, x, chain, *params):
+        _require_gpu(x, 'dcrdb')
+        x, ldx = _rowld(x)
+        n, _, h, w = x.shape
+        rows = n * h * w
+        a = b = RES_SCALE
+        bufs = [_adopt_or_fill(x, ldx, n, h, w)]
+        t3 = None
+        for k in range(3):
+            buf = bufs[k]
+            c5 = _dense_fwd(buf, params[10 * k:10 * k + 10], n, h, w, LRELU_SLOPE)
+            if k < 2:
+                nxt = _dense_buffer(n, h, w, x)
+                scaled_res_raw(buf, DENSE_W, c5, DENSE_NF, buf, DENSE_W, a, b, None, 0, nxt, DENSE_W, rows)
+                bufs.append(nxt)
+            else:
+                t3 = empty_nhwc(n, DENSE_NF, h, w, x)
+                scaled_res_raw(buf, DENSE_W, c5, DENSE_NF, buf, DENSE_W, a, b, None, 0, t3, DENSE_NF, rows)
+        c4 = empty_nhwc(n, DENSE_NF, h, w, x)
+        conv2d_fwd_ld(t3, DENSE_NF, params[30], params[31], c4, DENSE_NF, n, h, w)
+        out, ldo = _result_tensor(x, chain)
+        scaled_res_raw(x, ldx, c4, DENSE_NF, x, ldx, a, b, None, 0, out, ldo, rows)
+        ctx.save_for_backward(t3, *bufs, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dS):
+        t3, b1, b2, b3, *params = ctx.saved_tensors
+        dS, lds = _rowld(dS)
+        n, _, h, w = dS.shape
+        a = b = RES_SCALE
+        ka, kb = a * b, 1.0 + b
+        dc4 = empty_nhwc(n, DENSE_NF, h, w, dS)
+        scaled_res_bwd_raw(dS, lds, None, 0, ka, 0.0, 0.0, dc4, DENSE_NF, None, 0, DENSE_NF, n * h * w)
+        gw4, gb4 = conv2d_wgrad_ld(t3, DENSE_NF, dc4, DENSE_NF, tuple(params[30].shape), n, h, w)
+        dz = empty_nhwc(n, DENSE_NF, h, w, dS)
+        conv2d_dgrad_ld(dc4, DENSE_NF, params[30], dz, DENSE_NF, n, h, w, accumulate=False)
+        ldz = DENSE_NF
+        per_block = [None, None, None]
+        for k, buf in ((2, b3), (1, b2), (0, b1)):
+            grads = []
+            # the step's input x reaches S directly and through DCRDB's own residual: (1 + .2) dS, folded into block 1's pass
+            e, lde = (dS, lds) if k == 0 else (None, 0)
+            dbuf = _dense_bwd(buf, params[10 * k:10 * k + 10], dz, ldz, e, lde, ka, kb, kb, n, h, w, LRELU_SLOPE, grads)
+            per_block[k] = grads
+            dz, ldz = dbuf[:, :DENSE_NF], DENSE_W
+        return (dz, None) + tuple(per_block[0] + per_block[1] + per_block[2]) + (gw4, gb4)
+
+
+def dcrdb_step(x, params, chain=False):
+    """x + 0.2 * DCRDB(x) (one term of ndsrgan.py:121-158's running sum).  params: the 32 DCRDB tensors in state_dict order
+    (RDB1..3 each [CL weights / biases, conv5 weight, bias], then conv).  chain: the result is written into the next step's dense
+    buffer (the caller feeds it to another dcrdb_step)."""
+    return _DcrdbStep.apply(x, bool(chain), *params)
+
+
+class _ConvIntoDense(Function):
+    """conv 3x3 + bias (stride 1, 'same', 64 output channels) written into channels 0:64 of a new dense-block buffer: the generator's
+    conv1 (ndsrgan.py:164-167), whose output is the first DCRDB's input.  Returns that channel slice, tagged for adoption."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _require_gpu(x, 'conv2d_into_dense')
+        if w.shape[0] != DENSE_NF or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError('conv2d_into_dense: a 3x3 conv to 64 channels, got weight %s' % (tuple(w.shape),))
+        x, ldx = _rowld(x)
+        n, _, h, wd = x.shape
+        out, ldo = _result_tensor(x, True)
+        conv2d_fwd_ld(x, ldx, w, b, out, ldo, n, h, wd)
+        ctx.save_for_backward(x, w, b)
+        ctx.ldx = ldx
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        dy, ldy = _rowld(dy)
+        n, cin, h, wd = x.shape
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = empty_nhwc(n, cin, h, wd, dy)
+            conv2d_dgrad_ld(dy, ldy, w, dx, cin, n, h, wd, accumulate=False)
+        dw, db = conv2d_wgrad_ld(x, ctx.ldx, dy, ldy, tuple(w.shape), n, h, wd, with_bias=b is not None)
+        return dx, dw, db
+
+
+def conv2d_into_dense(x, weight, bias):
+    return _ConvIntoDense.apply(x, weight, bias)
+
+
+class _ConvResidualStrided(Function):
+    """conv 3x3 (x) + bias + r, r read through its own row stride: the generator's `out + conv2(trunk)` (ndsrgan.py:203) with `out`
+    the channel slice of the first dense buffer that conv1 wrote (no copy of it).  Output dense."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, r):
+        _require_gpu(x, 'conv2d_residual_strided')
+        x, ldx = _rowld(x)
+        r, ldr = _rowld(r)
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        y = empty_nhwc(n, cout, h, wd, x)
+        bias = b.detach().contiguous()
+        _hip.check(_hip.lib().srhip_conv2d_fwd(_p(x), _p(packed_weight(w, 0)), _p(bias), _p(r), None, None, _p(y), n, h, wd, cin, cout,
+                                               3, 3, 1, 1, ldx, cout, ldr, 0.0, EPI_BIAS | EPI_RESIDUAL, _stream()),
+                   'conv2d_fwd (strided residual)')
+        ctx.save_for_backward(x, w, b)
+        ctx.ldx = ldx
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        dy = nhwc(dy)
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = empty_nhwc(n, cin, h, wd, dy)
+            conv2d_dgrad_ld(dy, cout, w, dx, cin, n, h, wd, accumulate=False)
+        dw, db = conv2d_wgrad_ld(x, ctx.ldx, dy, cout, tuple(w.shape), n, h, wd)
+        return dx, dw, db, dy
+
+
+def conv2d_residual_strided(x, weight, bias, residual):
+    return _ConvResidualStrided.apply(x, weight, bias, residual)
+
+
+class _UpsampleNearest(Function):
+    """nn.UpsamplingNearest2d(scale_factor = r), r in {2, 3} (ndsrgan.py:175-181), NHWC."""
+
+    @staticmethod
+    def forward(ctx, x, r):
+        _require_gpu(x, 'upsample_nearest')
+        x = nhwc(x)
+        n, c, h, w = x.shape
+        y = empty_nhwc(n, c, h * r, w * r, x)
+        _hip.check(_hip.lib().srhip_upsample_nearest_fwd(_p(x), _p(y), n, h, w, c, r, _stream()), 'upsample_nearest_fwd')
+        ctx.r, ctx.shape = r, (n, c, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _UpsampleNearestBwd.apply(g, ctx.r, ctx.shape), None
+
+
+class _UpsampleNearestBwd(Function):
+    @staticmethod
+    def forward(ctx, g, r, shape):
+        g = nhwc(g)
+        n, c, h, w = shape
+        dx = empty_nhwc(n, c, h, w, g)
+        _hip.check(_hip.lib().srhip_upsample_nearest_bwd(_p(g), _p(dx), n, h, w, c, r, _stream()), 'upsample_nearest_bwd')
+        ctx.r = r
+        return dx
+
+    @staticmethod
+    def backward(ctx, gg):
+        return _UpsampleNearest.apply(gg, ctx.r), None, None
+
+
+def upsample_nearest(x, r):
+    return _UpsampleNearest.apply(x, int(r))
+
+
+class _SmoothL1Mean(Function):
+    @staticmethod
+    def forward(ctx, a, b, target):
+        _require_gpu(a, 'smooth_l1_mean')
+        a = nhwc(a) if a.dim() == 4 else a.contiguous()
+        if b is not None:
+            b = b.contiguous(memory_format=CL) if b.dim() == 4 else b.contiguous()
+            if a.shape != b.shape:
+                raise ValueError('smooth_l1_mean: shapes differ: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
+        lib = _hip.lib()
+        out = torch.empty((), device=a.device, dtype=torch.float32)
+        ws = _ws(lib.srhip_reduce_workspace(), a)
+        _hip.check(lib.srhip_smooth_l1_mean_fwd(_p(a), _p(b), float(target), _p(out), _p(ws), ws.numel() * 4, a.numel(), _stream()),
+                   'smooth_l1_mean_fwd')
+        ctx.save_for_backward(a, b)
+        ctx.target = float(target)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        need_b = b is not None and ctx.needs_input_grad[1]
+        like = (lambda: torch.empty_like(a, memory_format=CL)) if a.dim() == 4 else (lambda: torch.empty_like(a))
+        da = like()
+        db = like() if need_b else None
+        _hip.check(_hip.lib().srhip_smooth_l1_mean_bwd(_p(a), _p(b), ctx.target, _p(gout.contiguous()), _p(da), _p(db), a.numel(),
+                                                       _stream()), 'smooth_l1_mean_bwd')
+        return (da if ctx.needs_input_grad[0] else None), db, None
+
+
+def smooth_l1_mean(a, target):
+    """nn.SmoothL1Loss() (beta = 1, mean) of a against a tensor or a scalar target (D's valid = 1 / fake = 0 patches: no ones
+    tensor)."""
+    if torch.is_tensor(target):
+        return _SmoothL1Mean.apply(a, target, 0.0)
+    return _SmoothL1Mean.apply(a, None, float(target))
