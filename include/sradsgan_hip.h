@@ -57,7 +57,10 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  * ABI 12: DSSR's average-pool channel attention (srhip_ca_*), the upsampler fold passes (srhip_add_bcast_scaled,
  *         srhip_batch_sum_scaled) and srhip_mse_mean_* added (no existing entry point changed).
  * ABI 13: NDSRGAN's passes (srhip_scaled_res_fwd / _bwd, srhip_lrelu_bwd_strided, srhip_upsample_nearest_fwd / _bwd) and
- *         srhip_smooth_l1_mean_* added (no existing entry point changed). */
+ *         srhip_smooth_l1_mean_* added (no existing entry point changed).
+ * ABI 14: AMSSRN's passes: dilated 3x3 convolutions (srhip_conv2d_*_dil, srhip_conv2d_dil_workspace), PReLU with a
+ *         device-resident slope (srhip_prelu_*), quadrant non-local attention (srhip_nl_quad_*) and the gamma residual
+ *         (srhip_gamma_*) added (no existing entry point changed). */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -306,6 +309,51 @@ int srhip_lrelu_bwd_strided(const float* dy, int ldg, const float* y, int ldy, f
                             void* stream);
 int srhip_upsample_nearest_fwd(const float* x, float* y, int n, int h, int w, int c, int r, void* stream);
 int srhip_upsample_nearest_bwd(const float* dy, float* dx, int n, int h, int w, int c, int r, void* stream);
+/* ABI 14 -- dilated 3x3 convolutions, stride 1, pad = dilation, dilation 1..3 (AMSSRN's ASPP, amssrn.py:200-217).  Same packed weight
+ * as a plain 3x3 conv of that shape (srhip_pack_weight), same arithmetic modes.  Channels and row strides % 4 == 0, 16-byte aligned
+ * tensors; x / dx / dy / y rows have their own strides (ASPP writes its three outputs straight into one [n, h, w, 768] buffer).
+ * Dilation 1 is the plain 3x3 call.  Dilation d > 1 runs as the plain 3x3 conv of the d^2 polyphase sub-images (pixels with equal
+ * (h mod d, w mod d)) stacked as a batch of n d^2 images of ceil(h/d) x ceil(w/d) pixels: exact, and every kernel and knob of the plain
+ * path applies.  The workspace holds the gathered sub-images (srhip_conv2d_dil_workspace: kind 1 forward, 2 data gradient, 3 weight
+ * gradient; 0 bytes for dilation 1 except kind 3).
+ *   srhip_conv2d_fwd_dil  : y = act(conv(x [* chanscale[n][c]]) + bias); flags: SRHIP_EPI_BIAS | SRHIP_EPI_LRELU | SRHIP_EPI_CHANSCALE.
+ *   srhip_conv2d_dgrad_dil: dx (=|+=, accumulate) conv_transpose(dy, w).
+ *   srhip_conv2d_wgrad_dil: dw (OIHW) and db (optional) (=|+=, accumulate), from x and dy; accumulate only where
+ *                           srhip_conv2d_wgrad_can_accumulate(cin, cout, 3, 3) holds (the plain call's rule).                      */
+size_t srhip_conv2d_dil_workspace(int kind, int n, int h, int w, int cin, int cout, int dilation);
+int srhip_conv2d_fwd_dil(const float* x, const float* packed, const float* bias, const float* chanscale, float* y, void* workspace,
+                         size_t workspace_bytes, int n, int h, int w, int cin, int cout, int dilation, int ldx, int ldy, float slope,
+                         int flags, void* stream);
+int srhip_conv2d_dgrad_dil(const float* dy, const float* packed, float* dx, void* workspace, size_t workspace_bytes, int n, int h, int w,
+                           int cin, int cout, int dilation, int ldy, int ldx, int accumulate, void* stream);
+int srhip_conv2d_wgrad_dil(const float* x, const float* dy, float* dw, float* db, int accumulate, void* workspace, size_t workspace_bytes,
+                           int n, int h, int w, int cin, int cout, int dilation, int ldx, int ldy, void* stream);
+/* ABI 14 -- nn.PReLU() with one slope `a` that stays on the device (amssrn.py:176, 189, 212).  Rows are pixels with their own strides
+ * (multiples of 4, >= ch), ch % 4 == 0, 16-byte aligned; in place when the two tensors and their strides coincide (the
+ * backward: dz may alias g or z only with the same row stride).
+ *   srhip_prelu_fwd         : y = z > 0 ? z : a z.
+ *   srhip_prelu_bwd         : dz = z > 0 ? g : a g (from the pre-activation z, right for any sign of a), and the slope gradient
+ *                             sum (z > 0 ? 0 : z g) as srhip_prelu_parts() fixed-order partials.
+ *   srhip_prelu_slope_reduce: da (=|+=) the sum of nparts partials in a fixed order: one call over the partials of every application
+ *                             of a shared slope.  No atomics: reruns are bit-identical.                                           */
+int srhip_prelu_parts(void);
+int srhip_prelu_fwd(const float* z, int ldz, float* y, int ldy, const float* slope, long rows, int ch, void* stream);
+int srhip_prelu_bwd(const float* g, int ldg, const float* z, int ldz, float* dz, int lddz, const float* slope, float* partials, long rows,
+                    int ch, void* stream);
+int srhip_prelu_slope_reduce(const float* partials, int nparts, float* da, int accumulate, void* stream);
+/* ABI 14 -- AMSSRN's non-local attention on image quadrants (Nonlocal_CA, amssrn.py:93-165) and the gamma residual (:326-328).
+ *   srhip_nl_quad_fwd : per quadrant of the split at h / 2, w / 2, y = softmax(theta^T phi) g; theta, phi, g, y dense NHWC tensors of
+ *                       8 channels, [n, h, w, 8]; ml [n h w, 2] receives the row maximum and row sum of every query (for the backward).
+ *   srhip_nl_quad_bwd : dtheta, dphi, dg from dy (same layout); dd [n h w] is scratch (dy . y per query).  Exact fp32, no atomics.
+ *   srhip_gamma_res_fwd: out = a + gamma * b (gamma: one device float), dense, count % 4 == 0.
+ *   srhip_gamma_res_bwd: db = gamma * g (db may be NULL) and srhip_gamma_parts() fixed-order partials of sum(g * b) (reduce with
+ *                        srhip_prelu_slope_reduce).                                                                           */
+int srhip_nl_quad_fwd(const float* theta, const float* phi, const float* g, float* y, float* ml, int n, int h, int w, void* stream);
+int srhip_nl_quad_bwd(const float* theta, const float* phi, const float* g, const float* y, const float* ml, const float* dy, float* dd,
+                      float* dtheta, float* dphi, float* dg, int n, int h, int w, void* stream);
+int srhip_gamma_parts(void);
+int srhip_gamma_res_fwd(const float* a, const float* b, const float* gamma, float* out, long count, void* stream);
+int srhip_gamma_res_bwd(const float* g, const float* b, const float* gamma, float* db, float* partials, long count, void* stream);
 /* ABI 11: torch.cat(dim = 1) of n = 2..8 NHWC tensors with `rows` pixel rows each and chans[k] channels (multiples of 4, 16-byte aligned
  * tensors) -- the multi-scale block's three branches, sradsgan.py:340-344 -- and its backward: the wide tensor split back into n dense ones. */
 int srhip_cat_channels(const float* const* srcs, const int* chans, int n, float* out, long rows, void* stream);

@@ -139,6 +139,19 @@ SIGNATURES = {
     'srhip_lrelu_bwd_strided': (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _l, _i, _vp]),
     'srhip_upsample_nearest_fwd': (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
     'srhip_upsample_nearest_bwd': (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
+    'srhip_conv2d_dil_workspace': (_sz, [_i] * 7),
+    'srhip_conv2d_fwd_dil': (_i, [_vp] * 6 + [_sz] + [_i] * 8 + [_f, _i, _vp]),
+    'srhip_conv2d_dgrad_dil': (_i, [_vp] * 4 + [_sz] + [_i] * 9 + [_vp]),
+    'srhip_conv2d_wgrad_dil': (_i, [_vp] * 4 + [_i, _vp, _sz] + [_i] * 8 + [_vp]),
+    'srhip_prelu_parts': (_i, []),
+    'srhip_prelu_fwd': (_i, [_vp, _i, _vp, _i, _vp, _l, _i, _vp]),
+    'srhip_prelu_bwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _l, _i, _vp]),
+    'srhip_prelu_slope_reduce': (_i, [_vp, _i, _vp, _i, _vp]),
+    'srhip_nl_quad_fwd': (_i, [_vp] * 5 + [_i] * 3 + [_vp]),
+    'srhip_nl_quad_bwd': (_i, [_vp] * 10 + [_i] * 3 + [_vp]),
+    'srhip_gamma_parts': (_i, []),
+    'srhip_gamma_res_fwd': (_i, [_vp] * 4 + [_l, _vp]),
+    'srhip_gamma_res_bwd': (_i, [_vp] * 5 + [_l, _vp]),
     'srhip_cat_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_split_channels': (_i, [_vp, _vp, _i, _vp, _l, _vp]),
     'srhip_bn_train_bwd_acc': (_i, [_vp] * 12 + [_sz, _l, _i, _f, _i, _vp]),

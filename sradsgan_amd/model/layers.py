@@ -26,3 +26,29 @@ class HipBatchNorm2d(nn.BatchNorm2d):
 
     def forward(self, x, act_slope=None):
         return ops.batch_norm_act(x, self, act_slope)
+
+
+class HipDilatedConv2d(nn.Conv2d):
+    """nn.Conv2d(k = 3, stride 1, padding = dilation) with dilation 1..3 (AMSSRN's ASPP, amssrn.py:200-209) on the HIP dilated path.
+    HipConv2d keeps refusing dilation: its fused epilogues and data-gradient forms are the plain conv's."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        k, s, p, d = self.kernel_size, self.stride, self.padding, self.dilation
+        if k != (3, 3) or s != (1, 1) or d[0] != d[1] or p != d or not 1 <= d[0] <= ops.DIL_MAX or self.groups != 1:
+            raise NotImplementedError('HipDilatedConv2d: 3x3, stride 1, padding = dilation in 1..%d, groups 1 only' % ops.DIL_MAX)
+
+    def forward(self, x):
+        return ops.conv2d_dil(x, self.weight, self.bias, self.dilation[0])
+
+
+class HipPReLU(nn.PReLU):
+    """nn.PReLU() with one slope: y = z > 0 ? z : a z, the slope read on the device (no host synchronisation)."""
+
+    def __init__(self, num_parameters=1, init=0.25):
+        if num_parameters != 1:
+            raise NotImplementedError('HipPReLU: one slope per module (nn.PReLU())')
+        super().__init__(num_parameters, init)
+
+    def forward(self, x):
+        return ops.prelu(x, self.weight)

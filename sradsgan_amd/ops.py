@@ -2954,3 +2954,229 @@ def smooth_l1_mean(a, target):
     if torch.is_tensor(target):
         return _SmoothL1Mean.apply(a, target, 0.0)
     return _SmoothL1Mean.apply(a, None, float(target))
+
+
+# --------------------------------------------------------------------------------------------- #
+# AMSSRN's new arithmetic (SRADSGAN/model/amssrn.py:167-217): dilated 3x3 convolutions (csrc/conv_dilated.hip) and PReLU with a
+# device-resident slope (csrc/prelu.hip)
+# --------------------------------------------------------------------------------------------- #
+
+
+DIL_MAX = 3                                        # dilations 1..3 (ASPP's d1, d2, d3)
+
+
+def _dil_check(w_shape, dilation):
+    cout, cin, kh, kw = w_shape
+    if (kh, kw) != (3, 3) or not 1 <= dilation <= DIL_MAX or cin % 4 or cout % 4:
+        raise NotImplementedError('dilated conv: 3x3, dilation 1..%d, channels %% 4 == 0 (got %s, dilation %d)'
+                                  % (DIL_MAX, tuple(w_shape), dilation))
+    return cout, cin
+
+
+def _dil_workspace(kind, n, h, wd, cin, cout, dilation, like):
+    nbytes = _hip.lib().srhip_conv2d_dil_workspace(kind, n, h, wd, cin, cout, dilation)
+    return torch.empty(max((nbytes + 3) // 4, 4), device=like.device, dtype=torch.float32)
+
+
+def conv2d_dil_fwd_raw(x, ldx, w, b, y, ldy, n, h, wd, dilation, slope=None):
+    """y (rows of stride ldy) = act(conv(x, w, dilation) + b) for a stride-1 3x3 conv with pad = dilation; x: rows of stride ldx."""
+    _require_gpu(x, 'conv2d_fwd_dil')
+    cout, cin = _dil_check(w.shape, dilation)
+    flags = (EPI_BIAS if b is not None else 0) | (EPI_LRELU if slope is not None else 0)
+    bias = b.detach().contiguous() if b is not None else None
+    ws = _dil_workspace(1, n, h, wd, cin, cout, dilation, x)
+    _hip.check(_hip.lib().srhip_conv2d_fwd_dil(_p(x), _p(packed_weight(w, 0)), _p(bias), None, _p(y), _p(ws), ws.numel() * 4, n, h, wd,
+                                               cin, cout, dilation, ldx, ldy, float(slope or 0.0), flags, _stream()), 'conv2d_fwd_dil')
+
+
+def conv2d_dil_dgrad_raw(dy, ldy, w, dx, ldx, n, h, wd, dilation, accumulate=False):
+    """dx (rows of stride ldx) = / += conv_transpose(dy, w, dilation); dy: rows of stride ldy."""
+    _require_gpu(dy, 'conv2d_dgrad_dil')
+    cout, cin = _dil_check(w.shape, dilation)
+    ws = _dil_workspace(2, n, h, wd, cin, cout, dilation, dy)
+    _hip.check(_hip.lib().srhip_conv2d_dgrad_dil(_p(dy), _p(packed_weight(w, 1)), _p(dx), _p(ws), ws.numel() * 4, n, h, wd, cin, cout,
+                                                 dilation, ldy, ldx, int(accumulate), _stream()), 'conv2d_dgrad_dil')
+
+
+def conv2d_dil_wgrad_raw(x, ldx, dy, ldy, w_shape, n, h, wd, dilation, with_bias=True, out=None):
+    """(dw [OIHW], db or None) of a dilated 3x3 conv from x and dy (rows of strides ldx / ldy); out=(dw, db): accumulate into them."""
+    _require_gpu(x, 'conv2d_wgrad_dil')
+    cout, cin = _dil_check(w_shape, dilation)
+    ws = _dil_workspace(3, n, h, wd, cin, cout, dilation, x)
+    if out is None:
+        dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+        db = torch.empty(cout, device=x.device, dtype=torch.float32) if with_bias else None
+        acc = 0
+    else:
+        if not _hip.lib().srhip_conv2d_wgrad_can_accumulate(cin, cout, 3, 3):
+            raise NotImplementedError('conv2d_wgrad_dil: accumulating weight gradients need Cin %% 16 == 0 and Cout %% 4 == 0 '
+                                      '(srhip_conv2d_wgrad_can_accumulate), got %d -> %d' % (cin, cout))
+        (dw, db), acc = out, 1
+    _hip.check(_hip.lib().srhip_conv2d_wgrad_dil(_p(x), _p(dy), _p(dw), _p(db), acc, _p(ws), ws.numel() * 4, n, h, wd, cin, cout, dilation,
+                                                 ldx, ldy, _stream()), 'conv2d_wgrad_dil')
+    return dw, db
+
+
+class _ConvDil(Function):
+    """y = conv(x, w, dilation) + b, stride 1, pad = dilation (first-order: the generator-only AMSSRN step needs no double backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, dilation):
+        _require_gpu(x, 'conv2d_dil')
+        x = nhwc(x)
+        n, cin, h, wd = x.shape
+        if w.shape[1] != cin:
+            raise ValueError('conv2d_dil: weight expects %d input channels, got %d' % (w.shape[1], cin))
+        cout = w.shape[0]
+        y = empty_nhwc(n, cout, h, wd, x)
+        conv2d_dil_fwd_raw(x, cin, w, b, y, cout, n, h, wd, dilation)
+        ctx.dilation, ctx.has_bias = dilation, b is not None
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = nhwc(dy)
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = empty_nhwc(n, cin, h, wd, dy)
+            conv2d_dil_dgrad_raw(dy, cout, w, dx, cin, n, h, wd, ctx.dilation)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = conv2d_dil_wgrad_raw(x, cin, dy, cout, tuple(w.shape), n, h, wd, ctx.dilation, ctx.has_bias and ctx.needs_input_grad[2])
+            if not ctx.needs_input_grad[1]:
+                dw = None
+        return dx, dw, db, None
+
+
+def conv2d_dil(x, weight, bias=None, dilation=1):
+    """nn.Conv2d(k = 3, padding = dilation, dilation = dilation) forward on the HIP path.  x: logical NCHW; returns NHWC memory."""
+    return _ConvDil.apply(x, weight, bias, int(dilation))
+
+
+def prelu_fwd_raw(z, ldz, y, ldy, slope, rows, ch):
+    """y = z > 0 ? z : a z over `rows` pixel rows of ch channels (own row strides); slope: the 1-element device tensor a."""
+    _require_gpu(z, 'prelu_fwd')
+    _hip.check(_hip.lib().srhip_prelu_fwd(_p(z), ldz, _p(y), ldy, _p(slope.detach()), rows, ch, _stream()), 'prelu_fwd')
+
+
+def prelu_bwd_raw(g, ldg, z, ldz, dz, lddz, slope, partials, rows, ch):
+    """dz = z > 0 ? g : a g; writes srhip_prelu_parts() slope-gradient partials into `partials` (reduce with prelu_slope_reduce_raw)."""
+    _require_gpu(g, 'prelu_bwd')
+    _hip.check(_hip.lib().srhip_prelu_bwd(_p(g), ldg, _p(z), ldz, _p(dz), lddz, _p(slope.detach()), _p(partials), rows, ch, _stream()),
+               'prelu_bwd')
+
+
+def prelu_slope_reduce_raw(partials, da, accumulate=False):
+    """da (=|+=) the fixed-order sum of every partial in `partials`."""
+    _hip.check(_hip.lib().srhip_prelu_slope_reduce(_p(partials), partials.numel(), _p(da), int(accumulate), _stream()), 'prelu_slope_reduce')
+
+
+class _PReLU(Function):
+    @staticmethod
+    def forward(ctx, z, slope):
+        _require_gpu(z, 'prelu')
+        if slope.numel() != 1:
+            raise NotImplementedError('prelu: one slope per module (nn.PReLU()), got %d' % slope.numel())
+        z = nhwc(z)
+        n, c, h, w = z.shape
+        y = torch.empty_like(z, memory_format=CL)
+        prelu_fwd_raw(z, c, y, c, slope, n * h * w, c)
+        ctx.save_for_backward(z, slope)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, slope = ctx.saved_tensors
+        g = nhwc(g)
+        n, c, h, w = z.shape
+        dz = torch.empty_like(z, memory_format=CL)
+        partials = torch.empty(_hip.lib().srhip_prelu_parts(), device=z.device, dtype=torch.float32)
+        prelu_bwd_raw(g, c, z, c, dz, c, slope, partials, n * h * w, c)
+        da = torch.empty_like(slope)
+        prelu_slope_reduce_raw(partials, da)
+        return dz, da
+
+
+def prelu(z, slope):
+    """nn.PReLU() (one slope) on the HIP path; the slope stays on the device."""
+    return _PReLU.apply(z, slope)
+
+
+class _NonLocalQuad(Function):
+    """y = softmax(theta^T phi) g on each image quadrant (amssrn.py:103-165), 8 inter channels, NHWC [n, 8, h, w] operands."""
+
+    @staticmethod
+    def forward(ctx, th, ph, g):
+        _require_gpu(th, 'nl_quad')
+        th, ph, g = nhwc(th), nhwc(ph), nhwc(g)
+        n, c, h, w = th.shape
+        if c != 8 or ph.shape != th.shape or g.shape != th.shape:
+            raise NotImplementedError('nl_quad: theta, phi, g of 8 channels and one shape, got %s' % (tuple(th.shape),))
+        y = torch.empty_like(th, memory_format=CL)
+        ml = torch.empty(n * h * w * 2, device=th.device, dtype=torch.float32)
+        _hip.check(_hip.lib().srhip_nl_quad_fwd(_p(th), _p(ph), _p(g), _p(y), _p(ml), n, h, w, _stream()), 'nl_quad_fwd')
+        ctx.save_for_backward(th, ph, g, y, ml)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        th, ph, g, y, ml = ctx.saved_tensors
+        dy = nhwc(dy)
+        n, _, h, w = th.shape
+        dd = torch.empty(n * h * w, device=th.device, dtype=torch.float32)
+        dth, dph, dg = (torch.empty_like(th, memory_format=CL) for _ in range(3))
+        _hip.check(_hip.lib().srhip_nl_quad_bwd(_p(th), _p(ph), _p(g), _p(y), _p(ml), _p(dy), _p(dd), _p(dth), _p(dph), _p(dg), n, h, w,
+                                                _stream()), 'nl_quad_bwd')
+        return dth, dph, dg
+
+
+def nonlocal_quadrants(theta, phi, g):
+    return _NonLocalQuad.apply(theta, phi, g)
+
+
+class _GammaResidual(Function):
+    """out = a + gamma * b with gamma a 1-element device tensor (amssrn.py:327-328)."""
+
+    @staticmethod
+    def forward(ctx, a, b, gamma):
+        _require_gpu(a, 'gamma_res')
+        a, b = nhwc(a), nhwc(b)
+        out = torch.empty_like(a, memory_format=CL)
+        _hip.check(_hip.lib().srhip_gamma_res_fwd(_p(a), _p(b), _p(gamma.detach()), _p(out), a.numel(), _stream()), 'gamma_res_fwd')
+        ctx.save_for_backward(b, gamma)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        b, gamma = ctx.saved_tensors
+        g = nhwc(g)
+        lib = _hip.lib()
+        db = torch.empty_like(b, memory_format=CL) if ctx.needs_input_grad[1] else None
+        partials = torch.empty(lib.srhip_gamma_parts(), device=g.device, dtype=torch.float32)
+        _hip.check(lib.srhip_gamma_res_bwd(_p(g), _p(b), _p(gamma.detach()), _p(db), _p(partials), g.numel(), _stream()), 'gamma_res_bwd')
+        dgamma = torch.empty_like(gamma)
+        prelu_slope_reduce_raw(partials, dgamma)
+        return g, db, dgamma
+
+
+def gamma_residual(a, b, gamma):
+    return _GammaResidual.apply(a, b, gamma)
+
+
+def channel_attention_bias_prelu(x, w1, b1, slope, w2, b2):
+    """CALayer (amssrn.py:167-183) for any C % 4 == 0: x * sigmoid(conv_du(avgpool x)), conv_du = 1x1 (+bias), PReLU, 1x1 (+bias).
+    Pooling (srhip_cbam_pool_hw, mean half), the two 1x1 convs on [n, C, 1, 1], PReLU, sigmoid and the per-channel scale all run on
+    HIP kernels, each differentiable."""
+    n, c = x.shape[:2]
+    mean = _PoolHW.apply(x)[:, 0].reshape(n, c, 1, 1)
+    z = conv2d(mean, w1, b1)
+    u = conv2d(prelu(z, slope), w2, b2)
+    s = _Sigmoid.apply(nhwc(u), 0)
+    return _Scale.apply(x, s.reshape(n, c), 0)
