@@ -60,7 +60,10 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *         srhip_smooth_l1_mean_* added (no existing entry point changed).
  * ABI 14: AMSSRN's passes: dilated 3x3 convolutions (srhip_conv2d_*_dil, srhip_conv2d_dil_workspace), PReLU with a
  *         device-resident slope (srhip_prelu_*), quadrant non-local attention (srhip_nl_quad_*) and the gamma residual
- *         (srhip_gamma_*) added (no existing entry point changed). */
+ *         (srhip_gamma_*) added (no existing entry point changed).
+ *         Later in ABI 14, additive only: the channel attention with biases (srhip_ca_mlp_fwd_bias, srhip_ca_mlp_bwd_bias) for
+ *         RCAN.  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
+ *         declared symbol by name when it loads the library, so a library without them fails at load time. */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -286,6 +289,18 @@ int srhip_ca_mlp_bwd(const float* part, const float* avg, const float* hid, cons
                      float* dmean, float* dfc1, float* dfc2, void* workspace, size_t workspace_bytes, int n, int hw, int c, int hidden,
                      void* stream);
 int srhip_ca_bwd_du(const float* g, const float* s, const float* dmean, float* du, int n, int hw, int c, void* stream);
+/* ABI 14, additive -- RCAN's channel attention (model/drcan.py:94-111: CALayer.conv_du = 1x1 (+b1), ReLU, 1x1 (+b2), sigmoid) on the
+ * same kernels as the bias-free entries above; b1 [hidden], b2 [64], db1 [hidden], db2 [64]:
+ *   srhip_ca_mlp_fwd_bias : hid = relu(fc1 avg + b1), s = sigmoid(fc2 hid + b2)
+ *   srhip_ca_mlp_bwd_bias : srhip_ca_mlp_bwd plus db2[c] = sum_b dl[b,c] and db1[j] = sum_b dh[b,j] (dl = d(loss)/d(fc2 hid + b2),
+ *                           dh = d(loss)/d(fc1 avg + b1)), images summed in order in the weight-gradient pass
+ * Any bias pointer may be NULL: that bias is absent (forward) or its gradient is not written (backward).  With all of them NULL the
+ * results are bit-identical to srhip_ca_mlp_fwd / srhip_ca_mlp_bwd.  hidden = 4 and 16 are RCAN's reduction 16 and 4.           */
+int srhip_ca_mlp_fwd_bias(const float* psum, int nseg, const float* fc1, const float* b1, const float* fc2, const float* b2, float* avg,
+                          float* hid, float* s, int n, int hw, int c, int hidden, void* stream);
+int srhip_ca_mlp_bwd_bias(const float* part, const float* avg, const float* hid, const float* s, const float* fc1, const float* fc2,
+                          float* dmean, float* dfc1, float* db1, float* dfc2, float* db2, void* workspace, size_t workspace_bytes, int n,
+                          int hw, int c, int hidden, void* stream);
 int srhip_add_bcast_scaled(const float* a, const float* b, float scale, float* out, int n, long per_image, void* stream);
 int srhip_batch_sum_scaled(const float* g, float scale, float* out, int n, long per_image, void* stream);
 /* ABI 13 -- NDSRGAN (model/ndsrgan.py:57-211).  Rows are pixels; every operand has its own row stride (floats, multiple of 4, >= ch),

@@ -132,6 +132,8 @@ SIGNATURES = {
     'srhip_ca_mlp_bwd_workspace': (_sz, [_i, _i]),
     'srhip_ca_mlp_bwd': (_i, [_vp] * 10 + [_sz] + [_i] * 4 + [_vp]),
     'srhip_ca_bwd_du': (_i, [_vp] * 4 + [_i] * 3 + [_vp]),
+    'srhip_ca_mlp_fwd_bias': (_i, [_vp, _i] + [_vp] * 7 + [_i] * 4 + [_vp]),
+    'srhip_ca_mlp_bwd_bias': (_i, [_vp] * 12 + [_sz] + [_i] * 4 + [_vp]),
     'srhip_add_bcast_scaled': (_i, [_vp, _vp, _f, _vp, _i, _l, _vp]),
     'srhip_batch_sum_scaled': (_i, [_vp, _f, _vp, _i, _l, _vp]),
     'srhip_scaled_res_fwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _i, _vp, _i, _l, _i, _vp]),

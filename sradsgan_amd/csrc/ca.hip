@@ -1,5 +1,8 @@
 // Average-pool-only channel attention with the block's residual add (DSSR's WAB, reference model/dssr.py:69-104):
 //     s[n,c] = sigmoid(fc2 relu(fc1 mean_hw u))          out = s * u + x
+// with optional biases on the two 1x1 convs (RCAN's CALayer.conv_du, reference model/drcan.py:94-111):
+//     s[n,c] = sigmoid(fc2 relu(fc1 mean_hw u + b1) + b2)
+// NULL biases add nothing, so the bias-free entry points keep their arithmetic bit for bit.
 // and its backward, plus the two small passes of the DSSR upsampler fold (out = a + G * b broadcast over the batch and its
 // batch-sum backward).  u, x, g: NHWC, C == 64 channels, ld == C.  Every reduction is a fixed-order two-stage sum (per
 // (image, segment) partials, then one fixed walk over the segments): no atomics, bit-identical from run to run.
@@ -82,9 +85,10 @@ __device__ inline float ca_dot64(const float* __restrict__ row, const float* v) 
   return t;
 }
 
-// one block of 256 threads per image: avg, hidden = relu(fc1 avg), s = sigmoid(fc2 hidden)
+// one block of 256 threads per image: avg, hidden = relu(fc1 avg + b1), s = sigmoid(fc2 hidden + b2); b1 / b2 may be NULL
 __global__ __launch_bounds__(256) void ca_mlp_fwd_kernel(const float* __restrict__ psum, int nseg, float inv_hw,
-                                                         const float* __restrict__ fc1, const float* __restrict__ fc2,
+                                                         const float* __restrict__ fc1, const float* __restrict__ b1,
+                                                         const float* __restrict__ fc2, const float* __restrict__ b2,
                                                          float* __restrict__ avg, float* __restrict__ hid, float* __restrict__ s,
                                                          int hidden) {
   __shared__ float red[4][CA_C], sa[CA_C], sh[CA_MAXHID];
@@ -97,7 +101,9 @@ __global__ __launch_bounds__(256) void ca_mlp_fwd_kernel(const float* __restrict
   __syncthreads();
   const int j = t >> 4;
   if (j < hidden) {
-    const float v = fmaxf(ca_dot64(fc1 + j * CA_C, sa), 0.f);
+    float d = ca_dot64(fc1 + j * CA_C, sa);
+    if (b1) d += b1[j];
+    const float v = fmaxf(d, 0.f);
     if ((t & 15) == 0) {
       sh[j] = v;
       hid[b * hidden + j] = v;
@@ -107,6 +113,7 @@ __global__ __launch_bounds__(256) void ca_mlp_fwd_kernel(const float* __restrict
   if (t < CA_C) {
     float l = 0.f;
     for (int k = 0; k < hidden; ++k) l += fc2[t * hidden + k] * sh[k];
+    if (b2) l += b2[t];
     s[b * CA_C + t] = 1.f / (1.f + expf(-l));
   }
 }
@@ -157,10 +164,13 @@ __global__ __launch_bounds__(256) void ca_mlp_bwd_kernel(const float* __restrict
   }
 }
 
-// weight gradients, images in order: dfc2[c,j] = sum_b dl[b,c] hid[b,j], dfc1[j,c] = sum_b dh[b,j] avg[b,c]; one thread per element
+// weight gradients, images in order: dfc2[c,j] = sum_b dl[b,c] hid[b,j], dfc1[j,c] = sum_b dh[b,j] avg[b,c]; one thread per element.
+// Bias gradients (when db1 / db2 are not NULL), images in order: db2[c] = sum_b dl[b,c] (threads 0..63), db1[j] = sum_b dh[b,j]
+// (threads 0..hidden-1); 64 * hidden >= 64 threads, so every bias element has its thread.
 __global__ __launch_bounds__(256) void ca_mlp_wgrad_kernel(const float* __restrict__ dl, const float* __restrict__ dh,
                                                            const float* __restrict__ hid, const float* __restrict__ avg,
-                                                           float* __restrict__ dfc1, float* __restrict__ dfc2, int n, int hidden) {
+                                                           float* __restrict__ dfc1, float* __restrict__ dfc2,
+                                                           float* __restrict__ db1, float* __restrict__ db2, int n, int hidden) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= CA_C * hidden) return;
   const int c2 = i / hidden, j2 = i % hidden, j1 = i / CA_C, c1 = i % CA_C;
@@ -171,6 +181,16 @@ __global__ __launch_bounds__(256) void ca_mlp_wgrad_kernel(const float* __restri
   }
   dfc2[i] = g2;
   dfc1[i] = g1;
+  if (db2 && i < CA_C) {
+    float s2 = 0.f;
+    for (int b = 0; b < n; ++b) s2 += dl[b * CA_C + i];
+    db2[i] = s2;
+  }
+  if (db1 && i < hidden) {
+    float s1 = 0.f;
+    for (int b = 0; b < n; ++b) s1 += dh[b * hidden + i];
+    db1[i] = s1;
+  }
 }
 
 // du = s[n,c] * g + dmean[n,c]
@@ -228,14 +248,24 @@ int srhip_ca_pool_sum(const float* u, float* psum, int n, int hw, int c, void* s
   return check_launch("ca_pool_sum");
 }
 
+static int ca_mlp_fwd(const char* what, const float* psum, int nseg, const float* fc1, const float* b1, const float* fc2,
+                      const float* b2, float* avg, float* hid, float* s, int n, int hw, int c, int hidden, void* stream) {
+  SRHIP_REQUIRE(psum && fc1 && fc2 && avg && hid && s, "%s: null tensor", what);
+  SRHIP_REQUIRE(c == CA_C && hidden >= 1 && hidden <= CA_MAXHID && n > 0 && hw > 0 && nseg >= 1 && nseg <= POOL_MAXSEG,
+                "%s: C must be 64, 1 <= hidden <= 16, 1 <= nseg <= %d", what, POOL_MAXSEG);
+  hipLaunchKernelGGL(ca_mlp_fwd_kernel, dim3(n), dim3(256), 0, as_stream(stream), psum, nseg, (float)(1.0 / (double)hw), fc1, b1, fc2,
+                     b2, avg, hid, s, hidden);
+  return check_launch(what);
+}
+
 int srhip_ca_mlp_fwd(const float* psum, int nseg, const float* fc1, const float* fc2, float* avg, float* hid, float* s, int n, int hw,
                      int c, int hidden, void* stream) {
-  SRHIP_REQUIRE(psum && fc1 && fc2 && avg && hid && s, "ca_mlp_fwd: null tensor");
-  SRHIP_REQUIRE(c == CA_C && hidden >= 1 && hidden <= CA_MAXHID && n > 0 && hw > 0 && nseg >= 1 && nseg <= POOL_MAXSEG,
-                "ca_mlp_fwd: C must be 64, 1 <= hidden <= 16, 1 <= nseg <= %d", POOL_MAXSEG);
-  hipLaunchKernelGGL(ca_mlp_fwd_kernel, dim3(n), dim3(256), 0, as_stream(stream), psum, nseg, (float)(1.0 / (double)hw), fc1, fc2, avg,
-                     hid, s, hidden);
-  return check_launch("ca_mlp_fwd");
+  return ca_mlp_fwd("ca_mlp_fwd", psum, nseg, fc1, nullptr, fc2, nullptr, avg, hid, s, n, hw, c, hidden, stream);
+}
+
+int srhip_ca_mlp_fwd_bias(const float* psum, int nseg, const float* fc1, const float* b1, const float* fc2, const float* b2, float* avg,
+                          float* hid, float* s, int n, int hw, int c, int hidden, void* stream) {
+  return ca_mlp_fwd("ca_mlp_fwd_bias", psum, nseg, fc1, b1, fc2, b2, avg, hid, s, n, hw, c, hidden, stream);
 }
 
 int srhip_ca_scale_res(const float* u, const float* s, const float* x, float* out, int n, int hw, int c, void* stream) {
@@ -257,19 +287,34 @@ int srhip_ca_bwd_partial(const float* g, const float* u, float* part, int n, int
 
 size_t srhip_ca_mlp_bwd_workspace(int n, int hidden) { return (size_t)n * (CA_C + (hidden > 0 ? hidden : 0)) * sizeof(float); }
 
-int srhip_ca_mlp_bwd(const float* part, const float* avg, const float* hid, const float* s, const float* fc1, const float* fc2,
-                     float* dmean, float* dfc1, float* dfc2, void* workspace, size_t workspace_bytes, int n, int hw, int c, int hidden,
-                     void* stream) {
-  SRHIP_REQUIRE(part && avg && hid && s && fc1 && fc2 && dmean && dfc1 && dfc2, "ca_mlp_bwd: null tensor");
-  SRHIP_REQUIRE(c == CA_C && hidden >= 1 && hidden <= CA_MAXHID && n > 0 && hw > 0, "ca_mlp_bwd: C must be 64, 1 <= hidden <= 16");
-  SRHIP_REQUIRE(workspace && workspace_bytes >= srhip_ca_mlp_bwd_workspace(n, hidden), "ca_mlp_bwd: workspace too small");
+static int ca_mlp_bwd(const char* what, const float* part, const float* avg, const float* hid, const float* s, const float* fc1,
+                      const float* fc2, float* dmean, float* dfc1, float* db1, float* dfc2, float* db2, void* workspace,
+                      size_t workspace_bytes, int n, int hw, int c, int hidden, void* stream) {
+  SRHIP_REQUIRE(part && avg && hid && s && fc1 && fc2 && dmean && dfc1 && dfc2, "%s: null tensor", what);
+  SRHIP_REQUIRE(c == CA_C && hidden >= 1 && hidden <= CA_MAXHID && n > 0 && hw > 0, "%s: C must be 64, 1 <= hidden <= 16", what);
+  SRHIP_REQUIRE(workspace && workspace_bytes >= srhip_ca_mlp_bwd_workspace(n, hidden), "%s: workspace too small", what);
   float* dl = static_cast<float*>(workspace);
   float* dh = dl + (size_t)n * CA_C;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ca_mlp_bwd_kernel, dim3(n), dim3(256), 0, st, part, CA_SEG, hid, s, fc1, fc2, dmean, dl, dh, hidden,
                      (float)(1.0 / (double)hw));
-  hipLaunchKernelGGL(ca_mlp_wgrad_kernel, dim3(cdiv(CA_C * hidden, 256)), dim3(256), 0, st, dl, dh, hid, avg, dfc1, dfc2, n, hidden);
-  return check_launch("ca_mlp_bwd");
+  hipLaunchKernelGGL(ca_mlp_wgrad_kernel, dim3(cdiv(CA_C * hidden, 256)), dim3(256), 0, st, dl, dh, hid, avg, dfc1, dfc2, db1, db2, n,
+                     hidden);
+  return check_launch(what);
+}
+
+int srhip_ca_mlp_bwd(const float* part, const float* avg, const float* hid, const float* s, const float* fc1, const float* fc2,
+                     float* dmean, float* dfc1, float* dfc2, void* workspace, size_t workspace_bytes, int n, int hw, int c, int hidden,
+                     void* stream) {
+  return ca_mlp_bwd("ca_mlp_bwd", part, avg, hid, s, fc1, fc2, dmean, dfc1, nullptr, dfc2, nullptr, workspace, workspace_bytes, n, hw, c,
+                    hidden, stream);
+}
+
+int srhip_ca_mlp_bwd_bias(const float* part, const float* avg, const float* hid, const float* s, const float* fc1, const float* fc2,
+                          float* dmean, float* dfc1, float* db1, float* dfc2, float* db2, void* workspace, size_t workspace_bytes, int n,
+                          int hw, int c, int hidden, void* stream) {
+  return ca_mlp_bwd("ca_mlp_bwd_bias", part, avg, hid, s, fc1, fc2, dmean, dfc1, db1, dfc2, db2, workspace, workspace_bytes, n, hw, c,
+                    hidden, stream);
 }
 
 int srhip_ca_bwd_du(const float* g, const float* s, const float* dmean, float* du, int n, int hw, int c, void* stream) {

@@ -1,6 +1,6 @@
-"""The two blocks of the reference's model/base_networks.py that the SRADSGAN path reaches:
-ChannelAttention (base_networks.py:366-403) and SpatialAttention (:424-457), used by the
-discriminator (sradsgan.py:495-496).  They are arithmetically the generator's CLAM / SLAM."""
+"""The blocks of the reference's model/base_networks.py that the HIP path reaches: ChannelAttention (base_networks.py:366-403)
+and SpatialAttention (:424-457), used by the discriminator (sradsgan.py:495-496) and arithmetically the generator's CLAM / SLAM;
+and the patch Discriminator (:1747-1805) that DRCAN trains against."""
 import torch.nn as nn
 
 from .. import ops
@@ -45,3 +45,26 @@ class ChannelAttention(_Clam):
 
 class SpatialAttention(_Slam):
     pass
+
+
+class Discriminator(nn.Module):
+    """base_networks.py:1747-1805: the 8-block patch discriminator with a choice of normalisation, spectral norm and the attention
+    pair after block 6.  With norm_type='batch' and no spectral norm it is, layer for layer and key for key, sradsgan.py's
+    discriminator (DRCAN's D is `attention=False`, drcan.py:507-508), and it runs on the same HIP blocks.  The other normalisations
+    and spectral norm are not built on the HIP path."""
+
+    def __init__(self, in_channels=3, norm_type='', use_spectralnorm=False, attention=False):
+        super().__init__()
+        if use_spectralnorm:
+            raise NotImplementedError('Discriminator: spectral norm is not built on the HIP path')
+        if norm_type != 'batch':
+            raise NotImplementedError("Discriminator: norm_type %r is not built on the HIP path; 'batch' is (DRCAN's "
+                                      "Discriminator(norm_type='batch'))" % (norm_type,))
+        from .sradsgan import Discriminator as _PatchD          # (imported here: sradsgan.py imports this module)
+        d = _PatchD(in_channels, attention=attention)
+        self.norm_type, self.attention = norm_type, attention
+        self.model, self._blocks = d.model, d._blocks
+
+    def forward(self, img):
+        from .sradsgan import Discriminator as _PatchD
+        return _PatchD.forward(self, img)

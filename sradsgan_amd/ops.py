@@ -2483,12 +2483,13 @@ def conv2d_pool(x, weight, bias=None):
 
 
 class _CaResidual(Function):
-    """out = sigmoid(fc2 relu(fc1 mean_hw u)) * u + x: dssr.py:69-82 (CA with the average pool only) and the `out += x` of WAB
-    (:103).  Three launches forward (pooling pass unless the conv that produced u left its sums, MLP, scale + add), four
-    backward (g * u partials, per-image MLP backward, MLP weight gradients, du); deterministic."""
+    """out = sigmoid(fc2 relu(fc1 mean_hw u + b1) + b2) * u + x: dssr.py:69-82 (CA with the average pool only, no biases) and the
+    `out += x` of WAB (:103); with the biases, RCAN's CALayer and the `res += x` of its RCAB (drcan.py:94-135).  Three launches
+    forward (pooling pass unless the conv that produced u left its sums, MLP, scale + add), four backward (g * u partials, per-image
+    MLP backward, MLP weight and bias gradients, du); deterministic.  Without biases the bias-free entry points run, unchanged."""
 
     @staticmethod
-    def forward(ctx, u, x, fc1_w, fc2_w, pool=None):
+    def forward(ctx, u, x, fc1_w, fc2_w, pool=None, fc1_b=None, fc2_b=None):
         _require_gpu(u, 'ca_residual')
         u, x = nhwc(u), nhwc(x)
         n, c, h, w = u.shape
@@ -2497,6 +2498,9 @@ class _CaResidual(Function):
         lib = _hip.lib()
         f32 = dict(device=u.device, dtype=torch.float32)
         hid = fc1_w.shape[0]
+        biased = fc1_b is not None or fc2_b is not None
+        if biased and ((fc1_b is not None and fc1_b.numel() != hid) or (fc2_b is not None and fc2_b.numel() != c)):
+            raise ValueError('ca_residual: fc1_b must have %d and fc2_b %d elements' % (hid, c))
         if pool is None:
             nseg = lib.srhip_ca_segments()
             psum = torch.empty(n * nseg * c, **f32)
@@ -2505,11 +2509,19 @@ class _CaResidual(Function):
             psum, nseg = pool                        # the sum section leads the conv epilogue's [sum | max | arg] buffer
         avg, s, hidden = torch.empty(n, c, **f32), torch.empty(n, c, **f32), torch.empty(n, hid, **f32)
         fc1c, fc2c = fc1_w.detach().contiguous(), fc2_w.detach().contiguous()
-        _hip.check(lib.srhip_ca_mlp_fwd(_p(psum), nseg, _p(fc1c), _p(fc2c), _p(avg), _p(hidden), _p(s), n, h * w, c, hid, _stream()),
-                   'ca_mlp_fwd')
+        if biased:
+            b1c = fc1_b.detach().contiguous() if fc1_b is not None else None
+            b2c = fc2_b.detach().contiguous() if fc2_b is not None else None
+            _hip.check(lib.srhip_ca_mlp_fwd_bias(_p(psum), nseg, _p(fc1c), _p(b1c), _p(fc2c),
+                                                 _p(b2c), _p(avg), _p(hidden), _p(s), n, h * w, c, hid,
+                                                 _stream()), 'ca_mlp_fwd_bias')
+        else:
+            _hip.check(lib.srhip_ca_mlp_fwd(_p(psum), nseg, _p(fc1c), _p(fc2c), _p(avg), _p(hidden), _p(s), n, h * w, c, hid,
+                                            _stream()), 'ca_mlp_fwd')
         out = torch.empty_like(u, memory_format=CL)
         _hip.check(lib.srhip_ca_scale_res(_p(u), _p(s), _p(x), _p(out), n, h * w, c, _stream()), 'ca_scale_res')
         ctx.save_for_backward(u, fc1c, fc2c, avg, hidden, s)
+        ctx.biased = (fc1_b is not None, fc2_b is not None)
         return out
 
     @staticmethod
@@ -2525,19 +2537,28 @@ class _CaResidual(Function):
         dmean = torch.empty(n, c, **f32)
         dfc1, dfc2 = torch.empty(fc1c.shape, **f32), torch.empty(fc2c.shape, **f32)
         ws = _ws(lib.srhip_ca_mlp_bwd_workspace(n, fc1c.shape[0]), u)
-        _hip.check(lib.srhip_ca_mlp_bwd(_p(part), _p(avg), _p(hidden), _p(s), _p(fc1c), _p(fc2c), _p(dmean), _p(dfc1), _p(dfc2),
-                                        _p(ws), ws.numel() * 4, n, h * w, c, fc1c.shape[0], _stream()), 'ca_mlp_bwd')
+        need = ctx.needs_input_grad
+        has1, has2 = ctx.biased
+        db1 = torch.empty(fc1c.shape[0], **f32) if has1 and need[5] else None
+        db2 = torch.empty(c, **f32) if has2 and need[6] else None
+        if has1 or has2:
+            _hip.check(lib.srhip_ca_mlp_bwd_bias(_p(part), _p(avg), _p(hidden), _p(s), _p(fc1c), _p(fc2c), _p(dmean), _p(dfc1),
+                                                 _p(db1), _p(dfc2), _p(db2),
+                                                 _p(ws), ws.numel() * 4, n, h * w, c, fc1c.shape[0], _stream()), 'ca_mlp_bwd_bias')
+        else:
+            _hip.check(lib.srhip_ca_mlp_bwd(_p(part), _p(avg), _p(hidden), _p(s), _p(fc1c), _p(fc2c), _p(dmean), _p(dfc1), _p(dfc2),
+                                            _p(ws), ws.numel() * 4, n, h * w, c, fc1c.shape[0], _stream()), 'ca_mlp_bwd')
         du = torch.empty_like(u, memory_format=CL)
         _hip.check(lib.srhip_ca_bwd_du(_p(g), _p(s), _p(dmean), _p(du), n, h * w, c, _stream()), 'ca_bwd_du')
-        need = ctx.needs_input_grad
         return (du if need[0] else None, _passed_through(g) if need[1] else None, dfc1 if need[2] else None,
-                dfc2 if need[3] else None, None)
+                dfc2 if need[3] else None, None, db1, db2)
 
 
-def ca_residual(u, x, fc1_w, fc2_w, pool=None):
-    """sigmoid(fc2(relu(fc1(avgpool u)))) * u + x (dssr.py:69-82, 103) for 64-channel u.  pool: (buffer, segments per image) from
-    conv2d_pool, whose leading section holds the channel sums of u; None runs a pooling pass."""
-    return _CaResidual.apply(u, x, fc1_w, fc2_w, pool)
+def ca_residual(u, x, fc1_w, fc2_w, pool=None, fc1_b=None, fc2_b=None):
+    """sigmoid(fc2(relu(fc1(avgpool u) + fc1_b)) + fc2_b) * u + x (dssr.py:69-82, 103; with the biases drcan.py:94-135) for 64-channel
+    u.  pool: (buffer, segments per image) from conv2d_pool, whose leading section holds the channel sums of u; None runs a pooling
+    pass.  fc1_b [hidden] / fc2_b [64]: the 1x1 convs' biases, optional; without them the arithmetic is DSSR's, bit for bit."""
+    return _CaResidual.apply(u, x, fc1_w, fc2_w, pool, fc1_b, fc2_b)
 
 
 class _AddBcastScaled(Function):

@@ -56,6 +56,8 @@ def weights_init_normal(m, mean=0.0, std=0.02):
 
 
 class SRADSGAN(object):
+    eval_label = 'sradsgan'          # metric key prefix of mfeNew_validate / mfeNew_validateByClass lines (bicubic_* / <label>_*)
+
     def __init__(self, args, train_loader=None, test_loader=None):
         for k in ('model_name', 'train_dataset', 'test_dataset', 'crop_size', 'test_crop_size', 'hr_height', 'hr_width',
                   'num_threads', 'num_channels', 'scale_factor', 'epoch', 'num_epochs', 'save_epochs', 'batch_size',
@@ -93,9 +95,12 @@ class SRADSGAN(object):
                                rla_mode='CA-SA', bla_mode='CA-SA', ga_mode='CA-SA', pool_mode='Avg|Max', addconv=True,
                                upscale_factor=self.scale_factor)                               # :669-671, :1263-1265
 
+    def _new_discriminator(self):
+        return Discriminator()
+
     def _build(self):
         self.generator = self._new_generator()
-        self.discriminator = Discriminator()
+        self.discriminator = self._new_discriminator()
         self.feature_extractor = FeatureExtractor()
         model_dir = os.path.join(self.save_dir, 'model')
         if self.epoch != 0:                                                                     # :705-711
@@ -266,14 +271,14 @@ class SRADSGAN(object):
 
     def mfeNew_validate(self, epoch=100, modelpath=None):
         """sradsgan.py:1258-1391: fresh generator, optional `modelpath` (strict=False), same averages and log line
-        (keys bicubic_* / sradsgan_*)."""
+        (keys bicubic_* / <eval_label>_*)."""
         self.generator = self._new_generator().to(self.device)
         if modelpath is not None:
             self.generator.load_state_dict(torch.load(modelpath, map_location='cpu'), strict=False)   # :1270-1271
             ckpt._after_load()
-        avg, elapsed = self._evaluate_loader(self.generator, 'sradsgan')
-        self._log_val(epoch, avg, elapsed, 'sradsgan')
-        return avg['sradsgan_psnr'], avg['sradsgan_ssim'], avg['sradsgan_ergas'], float('nan')
+        avg, elapsed = self._evaluate_loader(self.generator, self.eval_label)
+        self._log_val(epoch, avg, elapsed, self.eval_label)
+        return avg[self.eval_label + '_psnr'], avg[self.eval_label + '_ssim'], avg[self.eval_label + '_ergas'], float('nan')
 
     def mfeNew_validateByClass(self, epoch, save_img=False, modelpath=None):
         """sradsgan.py:1393-1601: the validation of mfeNew_validate once per class folder of the test set, one
@@ -292,12 +297,12 @@ class SRADSGAN(object):
             ckpt._after_load()
         start, totals, result = time.time(), {}, OrderedDict()
         for name, loader in loaders.items():
-            avg, _ = self._evaluate_loader(self.generator, 'sradsgan', loader=loader, totals=totals)
-            self._log_val(epoch, avg, time.time() - start, 'sradsgan', model=name)              # :1548-1564
+            avg, _ = self._evaluate_loader(self.generator, self.eval_label, loader=loader, totals=totals)
+            self._log_val(epoch, avg, time.time() - start, self.eval_label, model=name)              # :1548-1564
             result[name] = avg
         num = max(totals.pop('num', 0), 1)
         result['Total'] = {k: v / num for k, v in totals.items()}                               # :1568-1577
-        self._log_val(epoch, result['Total'], time.time() - start, 'sradsgan', model='Total')
+        self._log_val(epoch, result['Total'], time.time() - start, self.eval_label, model='Total')
         return result
 
     def mfe_test_single(self, img_fn, modelpath=None):
