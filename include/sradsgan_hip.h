@@ -62,7 +62,8 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *         device-resident slope (srhip_prelu_*), quadrant non-local attention (srhip_nl_quad_*) and the gamma residual
  *         (srhip_gamma_*) added (no existing entry point changed).
  *         Later in ABI 14, additive only: the channel attention with biases (srhip_ca_mlp_fwd_bias, srhip_ca_mlp_bwd_bias) for
- *         RCAN.  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
+ *         RCAN; HAT's window-transformer passes (srhip_hat_*: LayerNorm, GELU, window attention, channel attention at any
+ *         C <= 128 and the block combine).  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
  *         declared symbol by name when it loads the library, so a library without them fails at load time. */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
@@ -303,6 +304,47 @@ int srhip_ca_mlp_bwd_bias(const float* part, const float* avg, const float* hid,
                           int hw, int c, int hidden, void* stream);
 int srhip_add_bcast_scaled(const float* a, const float* b, float scale, float* out, int n, long per_image, void* stream);
 int srhip_batch_sum_scaled(const float* g, float scale, float* out, int n, long per_image, void* stream);
+/* ABI 14, additive -- HAT's window transformer (model/hat.py; csrc/hat.hip).  Tokens are NHWC rows of C = 96 floats (6 heads of 16).
+ * Every reduction is a fixed-order sum: the results are bit-identical from run to run.
+ *   srhip_hat_ln_fwd   : nn.LayerNorm(96) (eps 1e-5) per token: y, mean [tokens], rstd [tokens]
+ *   srhip_hat_ln_bwd   : dx (+ dadd when not NULL), dgamma / dbeta written (NULL: not written); part: float workspace
+ *                        [srhip_hat_ln_parts(tokens)][192]
+ *   srhip_hat_gelu_fwd / _bwd : nn.GELU() (erf) and its backward, count % 4 == 0, 16-byte aligned
+ *   srhip_hat_attn_fwd : window attention on qkv [n*h*w][288] (channel part * 96 + head * 16 + d, the qkv Linear's output):
+ *                        kind 0 = HAB's W-MSA (shift 0) / SW-MSA (shift ws/2: roll, and the shift mask's -100), kind 1 = OCAB's
+ *                        overlapping cross-attention (queries: ws x ws windows; keys / values: the (ws + ws/2)^2 unfold of the
+ *                        qkv output with zero padding).  table [(2L-1)^2][6] is the relative-position bias table, indexed
+ *                        modulo its size.  out [n*h*w][96] at the original pixel positions, lse [n*h*w][6] the rows' log-sum-exp.
+ *                        ws 8 or 9, h and w multiples of ws.
+ *   srhip_hat_attn_bwd : dqkv [n*h*w][288] (written) and dtable (written) from out, dout and lse; workspace >=
+ *                        srhip_hat_attn_bwd_workspace(kind, n, h, w, ws)
+ *   srhip_hat_ca_fwd   : CAB's channel attention, C <= 128, 1 <= hidden <= 16: s[n][C] = sigmoid(w2 relu(w1 mean_hw u + b1) + b2);
+ *                        mz [n][C + hidden] keeps the mean and the hidden units for the backward (b1 / b2 may be NULL)
+ *   srhip_hat_combine_fwd : HAB's out = (x + kb[b] a) + cs (s[b,c] u); kb NULL: 1; u NULL: no third term (the MLP branch)
+ *   srhip_hat_combine_bwd : da = kb[b] g; with u: du = cs s g + d(mean)/hw through the channel attention and its parameter
+ *                        gradients dw1 [hidden][C], db1, dw2 [C][hidden], db2 (written, images summed in order; NULL: not written);
+ *                        workspace >= srhip_hat_combine_bwd_workspace(n, C, hidden).  dx = g is the caller's.             */
+int srhip_hat_ln_parts(long tokens);
+int srhip_hat_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long tokens,
+                     void* stream);
+int srhip_hat_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dadd,
+                     float* dx, float* part, float* dgamma, float* dbeta, long tokens, void* stream);
+int srhip_hat_gelu_fwd(const float* x, float* y, long count, void* stream);
+int srhip_hat_gelu_bwd(const float* dy, const float* x, float* dx, long count, void* stream);
+int srhip_hat_attn_fwd(const float* qkv, const float* table, float* out, float* lse, int kind, int n, int h, int w, int ws, int shift,
+                       void* stream);
+size_t srhip_hat_attn_bwd_workspace(int kind, int n, int h, int w, int ws);
+int srhip_hat_attn_bwd(const float* qkv, const float* table, const float* out, const float* dout, const float* lse, float* dqkv,
+                       float* dtable, void* workspace, size_t workspace_bytes, int kind, int n, int h, int w, int ws, int shift,
+                       void* stream);
+int srhip_hat_ca_fwd(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* mz, int n,
+                     long hw, int c, int hidden, void* stream);
+int srhip_hat_combine_fwd(const float* x, const float* a, const float* kb, const float* u, const float* s, float* out, float cs, int n,
+                          long hw, int c, void* stream);
+size_t srhip_hat_combine_bwd_workspace(int n, int c, int hidden);
+int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
+                          const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                          size_t workspace_bytes, float cs, int n, long hw, int c, int hidden, void* stream);
 /* ABI 13 -- NDSRGAN (model/ndsrgan.py:57-211).  Rows are pixels; every operand has its own row stride (floats, multiple of 4, >= ch),
  * all pointers 16-byte aligned, ch % 4 == 0.  A dense block keeps its input and the four CL outputs in ONE [n, h, w, 192] buffer:
  * CL j reads channels 0 : 64+32j (srhip_conv2d_fwd ldx = 192) and writes 64+32j : 96+32j (ldy = 192), and the passes below write a

@@ -165,6 +165,18 @@ SIGNATURES = {
     'srhip_quant_sse': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'srhip_ssim_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'srhip_metric_finish': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
+    'srhip_hat_ln_parts': (_i, [_l]),
+    'srhip_hat_ln_fwd': (_i, [_vp] * 6 + [_l, _vp]),
+    'srhip_hat_ln_bwd': (_i, [_vp] * 10 + [_l, _vp]),
+    'srhip_hat_gelu_fwd': (_i, [_vp, _vp, _l, _vp]),
+    'srhip_hat_gelu_bwd': (_i, [_vp] * 3 + [_l, _vp]),
+    'srhip_hat_attn_fwd': (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    'srhip_hat_attn_bwd_workspace': (_sz, [_i] * 5),
+    'srhip_hat_attn_bwd': (_i, [_vp] * 8 + [_sz] + [_i] * 6 + [_vp]),
+    'srhip_hat_ca_fwd': (_i, [_vp] * 7 + [_i, _l, _i, _i, _vp]),
+    'srhip_hat_combine_fwd': (_i, [_vp] * 6 + [_f, _i, _l, _i, _vp]),
+    'srhip_hat_combine_bwd_workspace': (_sz, [_i] * 3),
+    'srhip_hat_combine_bwd': (_i, [_vp] * 14 + [_sz, _f, _i, _l, _i, _i, _vp]),
     'srhip_adam_step': (_i, [_vp] * 5 + [_l] + [_f] * 6 + [_vp]),
 }
 

@@ -264,8 +264,13 @@ class _PackRegistry:
 _registry = _PackRegistry()
 
 
+def _wshape(w):
+    """OIHW shape of a conv weight; a Linear weight [out, in] is the 1x1 conv [out, in, 1, 1] (same memory)."""
+    return tuple(w.shape) if w.dim() == 4 else (w.shape[0], w.shape[1], 1, 1)
+
+
 def _pack_now(w, mode, packed):
-    cout, cin, kh, kw = w.shape
+    cout, cin, kh, kw = _wshape(w)
     wd = w.detach().contiguous()
     _hip.check(_hip.lib().srhip_pack_weight(_p(wd), _p(packed), cout, cin, kh, kw, mode, _stream()), 'pack_weight')
 
@@ -285,7 +290,7 @@ def repack_all():
         blob = bytearray()
         for ent, w in zip(reg.entries, live):
             mode, packed = ent[1], ent[2]
-            cout, cin, kh, kw = w.shape
+            cout, cin, kh, kw = _wshape(w)
             fast = lib.srhip_packed_is_fast(cout, cin, kh, kw, mode)
             blob += struct.pack('<QQiiiiii', w.data_ptr(), packed.data_ptr(), cout, cin, kh, kw, mode, fast)
             ent[3] = w.data_ptr()
@@ -341,7 +346,7 @@ def mark_static(module):
 def packed_weight(w, mode):
     """OIHW weight -> GEMM operand.  Parameters get a persistent buffer (see _PackRegistry); other tensors
     (e.g. the weight cotangent of a second-order pass) are packed on the fly."""
-    cout, cin, kh, kw = w.shape
+    cout, cin, kh, kw = _wshape(w)
     lib = _hip.lib()
     if not isinstance(w, torch.nn.Parameter):
         packed = torch.empty(lib.srhip_packed_elems(cout, cin, kh, kw, mode), device=w.device, dtype=torch.float32)
@@ -386,7 +391,7 @@ def conv2d_fwd_raw(x, w, bias, stride, pad, slope=None, residual=None, rowscale=
     _require_gpu(x, 'conv2d_fwd')
     x = nhwc(x)
     n, cin, h, wd = x.shape
-    cout, cin_w, kh, kw = w.shape
+    cout, cin_w, kh, kw = _wshape(w)
     if cin_w != cin:
         raise ValueError('conv2d_fwd: weight expects %d input channels, got %d' % (cin_w, cin))
     ho, wo = _out_hw(h, wd, kh, stride, pad)
@@ -459,7 +464,7 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride, pad, residual=None, actmask=None, s
     _require_gpu(dy, 'conv2d_dgrad')
     dy = nhwc(dy)
     n, cin, h, wd = x_shape
-    cout, _, kh, kw = w.shape
+    cout, _, kh, kw = _wshape(w)
     dx = empty_nhwc(n, cin, h, wd, dy)
     if residual is not None:
         residual = nhwc(residual)
@@ -3201,3 +3206,207 @@ def channel_attention_bias_prelu(x, w1, b1, slope, w2, b2):
     u = conv2d(prelu(z, slope), w2, b2)
     s = _Sigmoid.apply(nhwc(u), 0)
     return _Scale.apply(x, s.reshape(n, c), 0)
+
+
+# --------------------------------------------------------------------------------------------- #
+# HAT (model/hat.py): nn.Linear on 1x1 conv routes, LayerNorm, GELU, window attention (SA / OCA), the HAB combine with CAB's
+# channel attention (csrc/hat.hip).  Tokens are the NHWC rows of logical [n, C, h, w] channels_last tensors.
+# --------------------------------------------------------------------------------------------- #
+
+
+HAT_SA, HAT_OCA = 0, 1
+
+
+class _Linear(Function):
+    """y = x W^T + b [+ residual] over the channels of every pixel: the 1x1 conv route with W [out, in] read as [out, in, 1, 1]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, residual):
+        y = conv2d_fwd_raw(x, w, b, 1, 0, None, residual)
+        ctx.save_for_backward(nhwc(x), w)
+        ctx.has_b, ctx.has_res = b is not None, residual is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = nhwc(dy)
+        dx = conv2d_dgrad_raw(dy, w, tuple(x.shape), 1, 0) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+            dw, db = conv2d_wgrad_raw(x, dy, _wshape(w), 1, 0, ctx.has_b)
+            dw = dw.view(w.shape)
+        return dx, dw, db, (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
+
+
+def linear(x, weight, bias=None, residual=None):
+    """nn.Linear(in, out) applied to the channel vector of every pixel of x [n, in, h, w] (NHWC memory) -> [n, out, h, w]."""
+    return _Linear.apply(x, weight, bias, residual)
+
+
+def _hat_tokens(x, c, what):
+    _require_gpu(x, what)
+    x = nhwc(x)
+    if x.dim() != 4 or x.shape[1] != c:
+        raise ValueError('%s: expected [n, %d, h, w], got %s' % (what, c, tuple(x.shape)))
+    return x
+
+
+class _LayerNorm(Function):
+    """nn.LayerNorm(96) over the channels of every pixel (eps 1e-5)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = _hat_tokens(x, 96, 'layer_norm')
+        tokens = x.numel() // 96
+        y = torch.empty_like(x, memory_format=CL)
+        stats = torch.empty(2, tokens, device=x.device, dtype=torch.float32)
+        _hip.check(_hip.lib().srhip_hat_ln_fwd(_p(x), _p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(y),
+                                               _p(stats[0]), _p(stats[1]), tokens, _stream()), 'hat_ln_fwd')
+        ctx.save_for_backward(x, weight, stats)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, stats = ctx.saved_tensors
+        dy = nhwc(dy)
+        tokens = x.numel() // 96
+        lib = _hip.lib()
+        dx = torch.empty_like(x, memory_format=CL)
+        part = torch.empty(lib.srhip_hat_ln_parts(tokens) * 192, device=x.device, dtype=torch.float32)
+        dg = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
+        db = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
+        _hip.check(lib.srhip_hat_ln_bwd(_p(dy), _p(x), _p(weight.detach().contiguous()), _p(stats[0]), _p(stats[1]), None, _p(dx),
+                                        _p(part), _p(dg), _p(db), tokens, _stream()), 'hat_ln_bwd')
+        return dx, dg, db
+
+
+def layer_norm(x, weight, bias):
+    return _LayerNorm.apply(x, weight, bias)
+
+
+class _Gelu(Function):
+    """nn.GELU() (erf form)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_gpu(x, 'gelu')
+        x = nhwc(x)
+        y = torch.empty_like(x, memory_format=CL)
+        _hip.check(_hip.lib().srhip_hat_gelu_fwd(_p(x), _p(y), x.numel(), _stream()), 'hat_gelu_fwd')
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dy = nhwc(dy)
+        dx = torch.empty_like(x, memory_format=CL)
+        _hip.check(_hip.lib().srhip_hat_gelu_bwd(_p(dy), _p(x), _p(dx), x.numel(), _stream()), 'hat_gelu_bwd')
+        return dx
+
+
+def gelu(x):
+    return _Gelu.apply(x)
+
+
+class _WindowAttention(Function):
+    """softmax(q k^T / 4 + table[rpi] [+ mask]) v per window and head, from the qkv Linear's output [n, 288, h, w]; the output
+    [n, 96, h, w] sits at the pixels' own positions (the reference's roll / partition / unfold / reverse are addressing)."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, kind, ws, shift):
+        qkv = _hat_tokens(qkv, 288, 'window_attention')
+        n, _, h, w = qkv.shape
+        out = empty_nhwc(n, 96, h, w, qkv)
+        lse = torch.empty(n * h * w * 6, device=qkv.device, dtype=torch.float32)
+        tab = table.detach().contiguous()
+        _hip.check(_hip.lib().srhip_hat_attn_fwd(_p(qkv), _p(tab), _p(out), _p(lse), kind, n, h, w, ws, shift, _stream()),
+                   'hat_attn_fwd')
+        ctx.save_for_backward(qkv, tab, out, lse)
+        ctx.cfg = (kind, ws, shift)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qkv, tab, out, lse = ctx.saved_tensors
+        kind, ws, shift = ctx.cfg
+        dout = nhwc(dout)
+        n, _, h, w = qkv.shape
+        lib = _hip.lib()
+        dqkv = torch.empty_like(qkv, memory_format=CL)
+        dtab = torch.empty_like(tab)
+        nbytes = lib.srhip_hat_attn_bwd_workspace(kind, n, h, w, ws)
+        wsp = torch.empty((nbytes + 3) // 4, device=qkv.device, dtype=torch.float32)
+        _hip.check(lib.srhip_hat_attn_bwd(_p(qkv), _p(tab), _p(out), _p(dout), _p(lse), _p(dqkv), _p(dtab), _p(wsp), nbytes, kind, n,
+                                          h, w, ws, shift, _stream()), 'hat_attn_bwd')
+        return dqkv, dtab, None, None, None
+
+
+def window_attention(qkv, table, kind, window_size, shift=0):
+    """kind HAT_SA: (shifted) window self-attention of a HAB; HAT_OCA: OCAB's overlapping cross-attention (shift 0)."""
+    return _WindowAttention.apply(qkv, table, kind, window_size, shift)
+
+
+class _HabCombine(Function):
+    """out = (x + kb[b] a) + cs (s[b,c] u), s = sigmoid(w2 relu(w1 mean_hw u + b1) + b2) (CAB's ChannelAttention, hat.py:94-107);
+    u None: out = x + kb[b] a.  kb None: 1."""
+
+    @staticmethod
+    def forward(ctx, x, a, u, w1, b1, w2, b2, kb, cs):
+        x = _hat_tokens(x, x.shape[1], 'hab_combine')
+        a = nhwc(a)
+        n, c, h, w = x.shape
+        lib = _hip.lib()
+        out = torch.empty_like(x, memory_format=CL)
+        s = mz = None
+        if u is not None:
+            u = nhwc(u)
+            hid = w1.shape[0]
+            s = torch.empty(n, c, device=x.device, dtype=torch.float32)
+            mz = torch.empty(n, c + hid, device=x.device, dtype=torch.float32)
+            if b1 is None or b2 is None:
+                raise ValueError('hab_combine: the channel attention has biases (nn.Conv2d default)')
+            _hip.check(lib.srhip_hat_ca_fwd(_p(u), _p(w1.detach().contiguous()), _p(b1.detach().contiguous()),
+                                            _p(w2.detach().contiguous()), _p(b2.detach().contiguous()), _p(s), _p(mz), n, h * w, c,
+                                            hid, _stream()), 'hat_ca_fwd')
+        _hip.check(lib.srhip_hat_combine_fwd(_p(x), _p(a), _p(kb), _p(u), _p(s), _p(out), float(cs), n, h * w, c, _stream()),
+                   'hat_combine_fwd')
+        ctx.save_for_backward(u, w1, w2, kb, s, mz)
+        ctx.cs, ctx.has_u = float(cs), u is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        u, w1, w2, kb, s, mz = ctx.saved_tensors
+        g = nhwc(g)
+        n, c, h, w = g.shape
+        lib = _hip.lib()
+        da = torch.empty_like(g, memory_format=CL)
+        if not ctx.has_u:
+            _hip.check(lib.srhip_hat_combine_bwd(_p(g), _p(kb), None, None, None, None, None, _p(da), None, None, None, None, None,
+                                                 None, 0, ctx.cs, n, h * w, c, 1, _stream()), 'hat_combine_bwd')
+            return g, da, None, None, None, None, None, None, None
+        hid = w1.shape[0]
+        du = torch.empty_like(g, memory_format=CL)
+        dw1, db1 = torch.empty_like(w1), torch.empty(hid, device=g.device, dtype=torch.float32)
+        dw2, db2 = torch.empty_like(w2), torch.empty(c, device=g.device, dtype=torch.float32)
+        nbytes = lib.srhip_hat_combine_bwd_workspace(n, c, hid)
+        wsp = torch.empty((nbytes + 3) // 4, device=g.device, dtype=torch.float32)
+        _hip.check(lib.srhip_hat_combine_bwd(_p(g), _p(kb), _p(u), _p(s), _p(mz), _p(w1.detach().contiguous()),
+                                             _p(w2.detach().contiguous()), _p(da), _p(du), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(wsp),
+                                             nbytes, ctx.cs, n, h * w, c, hid, _stream()), 'hat_combine_bwd')
+        return g, da, du, dw1, db1, dw2, db2, None, None
+
+
+def hab_combine(x, a, u=None, w1=None, b1=None, w2=None, b2=None, kb=None, conv_scale=0.01):
+    """HAB (hat.py:289): x + drop_path(a) + conv_scale * CAB(.) where CAB's output is u * ChannelAttention(u); kb [n] holds the
+    drop-path factors floor(keep + U) / keep (None: identity).  With u None: x + drop_path(a) (the MLP branch, hat.py:290)."""
+    if kb is not None:
+        kb = kb.detach().contiguous().float()
+    return _HabCombine.apply(x, a, u, w1, b1, w2, b2, kb, conv_scale)
