@@ -138,7 +138,7 @@ class GradSync:
     passes run BESIDE that backward, nothing was left to hide it under.)
 
     Device tensors: the collectives are RCCL calls through the C ABI (srhip_dp_allreduce_bucket, include/sradsgan_hip.h)
-    on a dedicated HIP stream, issued by a helper thread (_Enqueuer; SRHIP_DP_THREAD=0: by the caller); ordering against the
+    on a dedicated HIP stream, issued by a helper thread (_Enqueuer; host_sync mode: by the caller); ordering against the
     compute streams is by events only, the host never synchronises.  xGMI is point-to-point (7 links x ~153 GB/s per GPU): a part
     goes out as <= 32 MiB buckets so the ring's reduce-scatter of one bucket overlaps the all-gather of the previous one.
     CPU tensors (the gloo tests): the same object drives torch.distributed's asynchronous all_reduce.
@@ -160,7 +160,7 @@ class GradSync:
         self._comm_stream = None
         self._rccl_ready = False
         self._whole = set()          # tags whose pending exchange is a whole arena (no further part may join it)
-        self._enqueuer = None        # _Enqueuer (device path, unless SRHIP_DP_THREAD=0)
+        self._enqueuer = None        # _Enqueuer (device path, unless host_sync)
         self.parts = []              # (tag, part, first element, elements) of every start() with part=..., in issue order (tests, tools)
         self.timing = False          # True: the completion events of the parts carry timestamps and are kept in done_log (tools/step_timeline.py)
         self.done_log = []           # (tag, part, event on the comm stream)
@@ -185,7 +185,6 @@ class GradSync:
             raise NotImplementedError('GradSync: the device (RCCL) path runs over the default process group only; a sub-group '
                                       'would need its own communicator and rendezvous key')
         import ctypes
-        import os
         from . import _hip
         lib = _hip.lib()
         if device is not None:
@@ -208,8 +207,8 @@ class GradSync:
         # event wait for most of the step.  Measured on MI355X / ROCm 7.0 (single rank, profiles/r02_bench_n1_rccl_single_rank.json): parked on
         # a normal-priority queue that wait slows the compute streams' kernels by 12 % (75.1 vs 66.6 ms per step, with or
         # without an RCCL call behind it); on a high-priority queue the step costs 66.9 ms (+0.4 %).
-        self._comm_stream = torch.cuda.Stream(priority=0 if os.environ.get('SRHIP_DP_PRIO') == '0' else -1)
-        if os.environ.get('SRHIP_DP_THREAD', '1') == '1' and not self.host_sync:
+        self._comm_stream = torch.cuda.Stream(priority=-1)
+        if not self.host_sync:
             self._enqueuer = _Enqueuer(torch.cuda.current_device())
         self._rccl_ready = True
         _COMM_USERS += 1
@@ -260,24 +259,18 @@ class GradSync:
             return
         if flat.is_cuda:
             import ctypes
-            import os
             from . import _hip
             self.init_rccl(flat.device)
             lib, comm = _hip.lib(), self._comm_stream
             evs = list(events) if events is not None else [s.record_event() for s in (after or (torch.cuda.current_stream(),))]
-            fake = os.environ.get('SRHIP_DP_MODE') == 'fake'        # experiment: same stream / event structure, no RCCL call
             timing = self.timing
 
             def enqueue():
                 for ev in evs:
                     comm.wait_event(ev)                             # no host synchronisation
-                if fake:
-                    with torch.cuda.stream(comm):
-                        flat[:64].mul_(1.0)
-                else:
-                    for b in self.buckets(flat):
-                        _hip.check(lib.srhip_dp_allreduce_bucket(ctypes.c_void_p(b.data_ptr()), b.numel(),
-                                                                 ctypes.c_void_p(comm.cuda_stream)), 'dp_allreduce_bucket')
+                for b in self.buckets(flat):
+                    _hip.check(lib.srhip_dp_allreduce_bucket(ctypes.c_void_p(b.data_ptr()), b.numel(),
+                                                             ctypes.c_void_p(comm.cuda_stream)), 'dp_allreduce_bucket')
                 done = torch.cuda.Event(enable_timing=timing)
                 done.record(comm)
                 if timing:

@@ -308,9 +308,6 @@ def bump_weight_epoch():
     repack_all()
 
 
-_NO_PACK_FENCE = os.environ.get('SRHIP_NO_PACK_FENCE') == '1'     # debug: reproduces the unordered first step
-
-
 def _pack_fence(ent):
     """A packed image is written by a kernel on the stream that first needed it (lazily, in the first step: the weight-
     gradient stream packs VGG's weights for the real batch, the D stream packs the discriminator's data-gradient images
@@ -319,7 +316,7 @@ def _pack_fence(ent):
     had not packed yet -- zeros on fresh memory (a silently wrong first step), NaNs on recycled memory
     (tests/test_model_gpu.py::test_first_step_of_a_model_does_not_depend_on_allocator_history).  The entry carries the pack's event; a stream waits for it once."""
     ev = ent[5]
-    if ev is None or _NO_PACK_FENCE:
+    if ev is None:
         return
     cs = torch.cuda.current_stream()
     sid = cs.cuda_stream
@@ -430,12 +427,9 @@ def conv2d_fwd_raw(x, w, bias, stride, pad, slope=None, residual=None, rowscale=
     return y
 
 
-_POOL_EPI = os.environ.get('SRHIP_POOL_EPI', '1') == '1'      # A/B knob: 0 = the RAB tails run their own pooling pass over u
-
-
 def pool_epilogue_ok(x, w):
     """RAB conv2 + its CLAM pooling partials in one call (srhip_conv2d_fwd_pool): split-bf16, stride-1 3x3 to 64 channels."""
-    return (_POOL_EPI and x.is_cuda and get_conv_math() == 'bf16x3' and tuple(w.shape[2:]) == (3, 3) and w.shape[0] == 64
+    return (x.is_cuda and get_conv_math() == 'bf16x3' and tuple(w.shape[2:]) == (3, 3) and w.shape[0] == 64
             and w.shape[1] % 32 == 0)
 
 
@@ -486,7 +480,6 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride, pad, residual=None, actmask=None, s
 
 
 _SIDE_WS = {}
-_FORK_C = os.environ.get('SRHIP_FORK_C', '1') == '1'      # A/B knob: 0 = fork the side stream through torch events + a stream context
 
 
 def _side_workspace(nbytes, device, stream):
@@ -543,7 +536,7 @@ def _fork_side(side, handles=None):
         hs.update(handles)
     hs.discard(side.cuda_stream)
     for h in hs:
-        if _state.capturing or not _FORK_C:
+        if _state.capturing:
             side.wait_stream(torch.cuda.ExternalStream(h) if h else torch.cuda.default_stream())
         else:
             _hip.check(_hip.lib().srhip_stream_fork(ctypes.c_void_p(h), ctypes.c_void_p(side.cuda_stream)), 'stream_fork')
@@ -790,26 +783,14 @@ class _PlanePool:
 
 
 plane_pool = _PlanePool()
-if os.environ.get('SRHIP_PERS_GRID'):                          # experiment: blocks of the persistent patch kernel (default: 3 per CU / one per tile)
-    _hip.lib().srhip_debug_set(5, int(os.environ['SRHIP_PERS_GRID']))
-if os.environ.get('SRHIP_FLAT_BLOCKS'):                        # experiment: blocks of the 8-wave weight-gradient kernel (default: one per CU)
-    _hip.lib().srhip_debug_set(12, int(os.environ['SRHIP_FLAT_BLOCKS']))
-if os.environ.get('SRHIP_POOL_EPI_ANY'):                       # experiment: conv2's CLAM pooling epilogue at any launch size (B = 32: 768 tiles)
-    _hip.lib().srhip_debug_set(19, int(os.environ['SRHIP_POOL_EPI_ANY']))
-if os.environ.get('SRHIP_FLAT_F32_K8'):                       # experiment: 0 = a weight gradient with one fp32 operand takes the 4-wave flat kernel
-    _hip.lib().srhip_debug_set(14, int(os.environ['SRHIP_FLAT_F32_K8']))
-if os.environ.get('SRHIP_TAIL_DBG'):                           # A/B knob: bit 32 = the round-5 launch sequence of the tail's backward (7x7 data gradient as its own launch)
-    _hip.lib().srhip_debug_set(7, int(os.environ['SRHIP_TAIL_DBG']))
 _X_PP = os.environ.get('SRHIP_X_PP', '1') == '1'                # A/B knob: 0 = a RAB's input never arrives as planes (conversion pass for its weight gradient)
-_DU_PP = os.environ.get('SRHIP_DU_PP', '1') == '1'              # A/B knob: 0 = conv2's gradients read the fp32 du (split in the dgrad kernel, pp_from_f32 pass for the weight gradient)
-_PP_RAB = os.environ.get('SRHIP_PP_RAB', '1') == '1'          # A/B knob: 0 = the RAB keeps t / dt as fp32 tensors (rounds 1-4)
 _PP_SIGNS = os.environ.get('SRHIP_PP_SIGNS', '1') == '1'      # A/B knob: 0 = conv2's data gradient reads its LeakyReLU mask from t's hi plane (48 MB) instead of sign words (3 MB)
 
 
 def rab_planes_ok(x, w1, w2):
     """The RAB keeps its two 256-channel tensors as padded planes: split-bf16 arithmetic, 64 -> Cmid -> 64 with both 3x3 convs and
     both weight gradients served on planes."""
-    if not (_PP_RAB and x.is_cuda and get_conv_math() == 'bf16x3'):
+    if not (x.is_cuda and get_conv_math() == 'bf16x3'):
         return False
     n, c, h, w = x.shape
     cm = w1.shape[0]
@@ -817,9 +798,6 @@ def rab_planes_ok(x, w1, w2):
     return (tuple(w1.shape[2:]) == (3, 3) and tuple(w2.shape[2:]) == (3, 3) and w2.shape[0] == c and w2.shape[1] == cm
             and bool(lib.srhip_conv2d_pp_ok(n, h, w, c, cm)) and bool(lib.srhip_conv2d_pp_ok(n, h, w, cm, c))
             and (lib.srhip_conv2d_wgrad_pp_ok(n, h, w, c, cm) & 4) and (lib.srhip_conv2d_wgrad_pp_ok(n, h, w, cm, c) & 4))
-
-
-_WGRAD_PP_CONVERT = os.environ.get('SRHIP_WGRAD_PP_CONVERT', '1') == '1'   # 1 (default): a pp_from_f32 pass of the 64-channel operand on the weight-gradient stream (in-step +0.4 % over the kernel's own in-place split: profiles/r05_wgrad_flat.txt)
 
 
 def _to_planes(t, device):
@@ -830,7 +808,8 @@ def _to_planes(t, device):
 
 
 def _launch_wgrad_pp(items, side):
-    """items: [(x, dy, gw, gb, release)] of one shape: fp32 operands are converted to planes and the flat kernel runs, all on `side`
+    """items: [(x, dy, gw, gb, release)] of one shape: fp32 operands are converted to planes (a pp_from_f32 pass of the 64-channel
+    operand: in-step +0.4 % over the kernel's own in-place split, profiles/r05_wgrad_flat.txt) and the flat kernel runs, all on `side`
     (None: the current stream); pooled buffers go back to the pool with an event of that stream."""
     main = torch.cuda.current_stream()
     run_on = side if side is not None else main
@@ -839,13 +818,12 @@ def _launch_wgrad_pp(items, side):
         launch = []
         for x, dy, gw, gb, release in items:
             xo, dyo = x, dy
-            if _WGRAD_PP_CONVERT:                        # A/B knob: a stand-alone pp_from_f32 pass instead of the kernel's in-place split
-                if not isinstance(x, PP):
-                    xo = _to_planes(x, gw.device)
-                    conv.append(xo)
-                if not isinstance(dy, PP):
-                    dyo = _to_planes(dy, gw.device)
-                    conv.append(dyo)
+            if not isinstance(x, PP):
+                xo = _to_planes(x, gw.device)
+                conv.append(xo)
+            if not isinstance(dy, PP):
+                dyo = _to_planes(dy, gw.device)
+                conv.append(dyo)
             launch.append((xo, dyo, gw, gb))
         conv2d_wgrad_pp_raw(launch, accumulate=True, on_stream=side)
         for pp in conv:
@@ -892,10 +870,6 @@ def wgrad_pp_for_params(w, b, x, dy, want_b, release=()):
     return True
 
 
-_WGRAD_DEFER = os.environ.get('SRHIP_WGRAD_DEFER', '0') == '1'     # experiment: hold every groupable weight gradient until a flush point
-_WGRAD_FLUSH_GROUP = int(os.environ.get('SRHIP_WGRAD_FLUSH_GROUP', '0'))   # convolutions per launch at a flush (0: the step's group size)
-
-
 def _flush_key(key):
     items = _state.pending.pop(key, None)
     if not items:
@@ -906,29 +880,26 @@ def _flush_key(key):
         _launch_wgrad_pp([it[:5] for it in items], side)
         return
     _fork_side(side, [it[6] for it in items])
-    items = [it[:6] for it in items]
-    per = max(1, _WGRAD_FLUSH_GROUP or _state.wgrad_group)
-    for i0 in range(0, len(items), per):
-        chunk = items[i0:i0 + per]
-        if len(chunk) == 1:
-            x, dy, gw, gb, stride, pad = chunk[0]
-            if _state.capturing or not _FORK_C:
-                with torch.cuda.stream(side):
-                    conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb))
-            else:
-                conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb), on_stream=side)
-        elif _state.capturing or not _FORK_C:
+    items = [it[:6] for it in items]              # at most the step's group size: a queue goes out the moment it is that long
+    if len(items) == 1:
+        x, dy, gw, gb, stride, pad = items[0]
+        if _state.capturing:
             with torch.cuda.stream(side):
-                conv2d_wgrad_multi_raw(chunk)
+                conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb))
         else:
-            conv2d_wgrad_multi_raw(chunk, on_stream=side)
+            conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb), on_stream=side)
+    elif _state.capturing:
+        with torch.cuda.stream(side):
+            conv2d_wgrad_multi_raw(items)
+    else:
+        conv2d_wgrad_multi_raw(items, on_stream=side)
     for it in items:
         it[0].record_stream(side)
         it[1].record_stream(side)
         _hold_for_side(side, it[1])
 
 
-_WGRAD_MAX_AGE = int(os.environ.get('SRHIP_WGRAD_MAX_AGE', '14'))    # weight-gradient calls a launch may wait for a partner (0: until the next flush point)
+_WGRAD_MAX_AGE = 14    # weight-gradient calls a launch may wait for a partner
 
 
 def _age_pending():
@@ -937,7 +908,7 @@ def _age_pending():
     108^2) used to wait for the flush at the END of the generator's backward and then ran, alone on the chip, for 0.5 ms after the
     main stream had finished (`tools/step_tail.py`, profiles/r05_step_tail_before.txt)."""
     _state.wgrad_seq += 1
-    if not _WGRAD_MAX_AGE or _WGRAD_DEFER or not _state.pending:
+    if not _state.pending:
         return
     for key in [k for k, q in _state.pending.items() if q and _state.wgrad_seq - q[0][-1] > _WGRAD_MAX_AGE]:
         _flush_key(key)
@@ -946,7 +917,7 @@ def _age_pending():
 # RAB weight gradients of one shape per flat-kernel launch.  Round 6: 3 -- a ResGroup's three RABs -- instead of pairs: the launch keeps one
 # block per CU, so every convolution gets a third instead of half of the split-K splits (28 instead of 42): a third fewer partial tiles written and
 # reduced, and the launches line up with the group boundaries the exchange's parts are cut at.  +0.5 % same-box (profiles/r06_step_ab.txt; 4: the same)
-_PP_GROUP = max(2, min(4, int(os.environ.get('SRHIP_PP_GROUP', '3'))))
+_PP_GROUP = 3
 _WGRAD_SLOTS = os.environ.get('SRHIP_WGRAD_SLOTS', '0') == '1'     # experiment, OFF: see release_ready_pair (kernel-level effect as predicted, step unchanged)
 
 
@@ -1023,10 +994,10 @@ def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscal
             key = (tuple(x.shape), cout, stride, pad, gb is not None)
             q = _state.pending.setdefault(key, [])
             q.append((x, dy, gw, gb, stride, pad, _stream().value, _state.wgrad_seq))     # + the stream that produced the operands, + the request number
-            if len(q) >= _state.wgrad_group and not _WGRAD_DEFER:
+            if len(q) >= _state.wgrad_group:
                 _flush_key(key)
             return None, None
-        if _state.capturing or not _FORK_C:
+        if _state.capturing:
             main = torch.cuda.current_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -1066,9 +1037,6 @@ def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscal
         _hold_for_side(side, dy)
         return None, None
     return conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
-
-
-_WGRAD_ACT = os.environ.get('SRHIP_WGRAD_ACT', '1') == '1'      # A/B knob
 
 
 def _wgrad_act_direct(w, b, x, dy, y, slope, stride, pad):
@@ -1201,7 +1169,7 @@ class _ConvFwd(Function):
         skip = _skip_param_grads(w)
         need_dx = ctx.needs_input_grad[0] and x.data_ptr() not in _state.stop_ids
         if ctx.slope is not None and not need_dx and not skip and ctx.needs_input_grad[1] and ctx.has_bias and \
-                ctx.needs_input_grad[2] and _state.direct_grads and not torch.is_grad_enabled() and _WGRAD_ACT and \
+                ctx.needs_input_grad[2] and _state.direct_grads and not torch.is_grad_enabled() and \
                 _wgrad_act_direct(w, b, x, dy, y, ctx.slope, ctx.stride, ctx.pad):
             # head conv of the discriminator in the D step: only its parameter gradients are wanted, and the kernel applies the
             # activation's backward while it reads dy -- no lrelu-backward pass over the 382 MB gradient in the serial chain
@@ -1276,9 +1244,6 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act_slope=None, residual=N
     return _ConvFwd.apply(x, weight, bias, residual, stride, padding, act_slope)
 
 
-_BUS_SUM = os.environ.get('SRHIP_BUS_SUM', '1') == '1'      # A/B knob: 0 = chained torch adds
-
-
 class _SumN(Function):
     """((t0 + t1) + t2) + ... in one pass (srhip_sum_n); every term gets the incoming gradient, as with chained adds."""
 
@@ -1301,7 +1266,7 @@ class _SumN(Function):
 def sum_tensors(ts):
     """Sum of 2..16 same-shape NCHW tensors in the order given (the generator's bus); falls back to chained adds otherwise."""
     ts = list(ts)
-    if (_BUS_SUM and 2 <= len(ts) <= 16 and ts[0].is_cuda and ts[0].dim() == 4 and ts[0].numel() % 4 == 0
+    if (2 <= len(ts) <= 16 and ts[0].is_cuda and ts[0].dim() == 4 and ts[0].numel() % 4 == 0
             and all(t.shape == ts[0].shape and t.dtype == torch.float32 for t in ts)):
         return _SumN.apply(tuple(_carry_commit(t) for t in ts), *ts)
     out = ts[0]
@@ -1339,14 +1304,11 @@ class _CatChannels(Function):
         return tuple(outs)
 
 
-_CAT = os.environ.get('SRHIP_CAT', '1') == '1'     # A/B knob: 0 = torch.cat
-
-
 def cat_channels(ts):
     """torch.cat(ts, dim=1) for 2..8 same-size fp32 NCHW tensors whose channel counts are multiples of 4; torch.cat otherwise."""
     ts = list(ts)
-    if (_CAT and 2 <= len(ts) <= 8 and ts[0].is_cuda and all(t.dim() == 4 and t.dtype == torch.float32 and t.shape[1] % 4 == 0
-                                                                and t.shape[0] == ts[0].shape[0] and t.shape[2:] == ts[0].shape[2:] for t in ts)):
+    if (2 <= len(ts) <= 8 and ts[0].is_cuda and all(t.dim() == 4 and t.dtype == torch.float32 and t.shape[1] % 4 == 0
+                                                       and t.shape[0] == ts[0].shape[0] and t.shape[2:] == ts[0].shape[2:] for t in ts)):
         return _CatChannels.apply(*ts)
     return torch.cat(ts, dim=1)
 
@@ -1392,9 +1354,6 @@ def pixel_shuffle_act(x, r, slope=None):
 # --------------------------------------------------------------------------------------------- #
 
 
-_TAIL_FUSED = os.environ.get('SRHIP_TAIL_FUSED', '1') == '1'
-
-
 def _tail_forward(u, skip, fc1_w, fc2_w, w7, wc, bc, pool=None, out_pp=None):
     """returns (out, tensors to save for _tail_backward).  pool: (buffer, section bytes, nseg) from conv2d_fwd_pool_raw -- the
     pooling partials of u left behind by the conv that produced it (else the tail runs its own pooling pass)."""
@@ -1422,7 +1381,7 @@ def _tail_forward(u, skip, fc1_w, fc2_w, w7, wc, bc, pool=None, out_pp=None):
 
 def _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, has_bias, skip_params=False, du_pp=None):
     """g: gradient at the tail's output (NHWC).  Returns (du, dfc1, dfc2, dw7, dwc, dbc).  du_pp: a PP buffer that receives du as
-    padded planes INSTEAD of the fp32 tensor (du is then returned as None; fused path only: the caller checks `_TAIL_FUSED`)."""
+    padded planes INSTEAD of the fp32 tensor (du is then returned as None)."""
     avg, mx, arg, s, pooled, argc, m = saved
     n, c, h, w = u.shape
     lib = _hip.lib()
@@ -1439,19 +1398,6 @@ def _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, has_bias, skip_params=
     dw7 = g7 if g7 is not None else torch.empty(w7.shape, **f32)
     dfc1 = g1 if direct else torch.empty(fc1_w.shape, **f32)
     dfc2 = g2 if direct else torch.empty(fc2_w.shape, **f32)
-    if not _TAIL_FUSED:                                        # A/B knob: the three separate entry points (10 launches)
-        ds = torch.empty(n, c, **f32)
-        ws = torch.empty(lib.srhip_attn_tail_bwd_workspace(n, h, w) // 4, **f32)
-        _hip.check(lib.srhip_attn_tail_bwd_spatial(_p(dz), _p(u), _p(s), _p(m), _p(pooled), _p(argc), _p(w7.detach().contiguous()),
-                                                   _p(du), _p(ds), _p(dw7), int(g7 is not None), _p(ws), ws.numel() * 4, n, h, w, c,
-                                                   _stream()), 'attn_tail_bwd_spatial')
-        davg, dmax = torch.empty(n, c, **f32), torch.empty(n, c, **f32)
-        ws2 = torch.empty(lib.srhip_attn_tail_mlp_workspace(n, hid) // 4, **f32)
-        _hip.check(lib.srhip_attn_tail_bwd_mlp(_p(ds), _p(avg), _p(mx), _p(s), _p(fc1_w.detach().contiguous()),
-                                               _p(fc2_w.detach().contiguous()), _p(davg), _p(dmax), _p(dfc1), _p(dfc2), int(direct),
-                                               _p(ws2), ws2.numel() * 4, n, c, hid, _stream()), 'attn_tail_bwd_mlp')
-        _hip.check(lib.srhip_attn_tail_bwd_channel(_p(du), _p(davg), _p(dmax), _p(arg), n, h, w, c, _stream()), 'attn_tail_bwd_channel')
-        return du, (None if direct else dfc1), (None if direct else dfc2), (None if g7 is not None else dw7), dwc, dbc
     # spatial half (7x7 conv, per-pixel gate), channel half (sigmoid -> shared MLP) and the arg-max fix-up: one call
     ws = torch.empty(lib.srhip_attn_tail_bwd_fused_workspace(n, h, w, hid) // 4, **f32)
     _hip.check(lib.srhip_attn_tail_bwd_pp(_p(dz), _p(u), _p(s), _p(m), _p(pooled), _p(argc), _p(avg), _p(mx), _p(arg),
@@ -1468,12 +1414,9 @@ def _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, has_bias, skip_params=
     return du, dfc1, dfc2, dw7, dwc, dbc
 
 
-_TAIL_EVAL = os.environ.get('SRHIP_TAIL_EVAL', '1') == '1'      # A/B knob: 0 = the training-mode launches in inference as well
-
-
 def _tail_eval_ok(u):
     """Inference fast path (srhip_attn_tail_eval): grad mode off, split-bf16 arithmetic, a CUDA tensor."""
-    return _TAIL_EVAL and not torch.is_grad_enabled() and u.is_cuda and get_conv_math() == 'bf16x3'
+    return not torch.is_grad_enabled() and u.is_cuda and get_conv_math() == 'bf16x3'
 
 
 def _tail_forward_eval(u, skip, fc1_w, fc2_w, w7, wc, bc, pool=None):
@@ -1577,7 +1520,7 @@ class _RabBlock(Function):
             # the pooled plane buffers (t, x, sign words) went back to the pool with the first backward: there is nothing to run a
             # second one on (retain_graph) -- say so instead of unpacking saved_tensors in the fp32 path's order
             raise RuntimeError('_RabBlock: backward called twice on the padded-plane path (its plane buffers are released by the first '
-                               'backward); run the forward again, or set SRHIP_PP_RAB=0 for a graph that is walked repeatedly')
+                               'backward); run the forward again')
         x, t, u, w1, b1, w2, b2, fc1_w, fc2_w, w7, wc, bc, *saved = ctx.saved_tensors
         g = nhwc(g)
         skip = _skip_param_grads()
@@ -1604,11 +1547,11 @@ class _RabBlock(Function):
         n, _, h, wd = x.shape
         # the tail's backward leaves du as fp32 (the gradient of the block's residual stream) AND as padded planes: conv2's data and
         # weight gradient read the planes (no in-kernel split, no conversion pass)
-        du_pp = plane_pool.get(n, u.shape[1], h, wd, x.device) if (_TAIL_FUSED and _DU_PP) else None
+        du_pp = plane_pool.get(n, u.shape[1], h, wd, x.device)
         du, dfc1, dfc2, dw7, dwc, dbc = _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, ctx.has_b[2], skip, du_pp)
         dt_pp = plane_pool.get(n, w1.shape[0], h, wd, x.device)
         signs, ctx.signs = ctx.signs, None
-        conv2d_dgrad_pp_raw(du_pp if du_pp is not None else du, w2, actmask=t_pp if signs is None else None, slope=0.2, out_pp=dt_pp, signs=signs)   # * LeakyReLU'(t), planes out
+        conv2d_dgrad_pp_raw(du_pp, w2, actmask=t_pp if signs is None else None, slope=0.2, out_pp=dt_pp, signs=signs)   # * LeakyReLU'(t), planes out
         dw2 = db2 = dw1 = db1 = None
         main = torch.cuda.current_stream()
         t_done = dt_done = False
@@ -1617,10 +1560,9 @@ class _RabBlock(Function):
             dx = conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None
             release_ready_pair(1)
         if not skip:
-            t_done = wgrad_pp_for_params(w2, b2, t_pp, du_pp if du_pp is not None else du, ctx.has_b[1],
-                                         release=(t_pp,) if du_pp is None else (t_pp, du_pp))
+            t_done = wgrad_pp_for_params(w2, b2, t_pp, du_pp, ctx.has_b[1], release=(t_pp, du_pp))
             if not t_done:                                # autograd wants the gradients returned: the fp32 path on converted operands
-                dw2, db2 = wgrad_for_params(w2, b2, pp_to_f32(t_pp), du if du is not None else pp_to_f32(du_pp), 1, 1, ctx.has_b[1])
+                dw2, db2 = wgrad_for_params(w2, b2, pp_to_f32(t_pp), pp_to_f32(du_pp), 1, 1, ctx.has_b[1])
         if not slots:
             dx = conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None   # + skip gradient (+ the input's stashed gradients)
         if not skip:
@@ -1630,8 +1572,7 @@ class _RabBlock(Function):
                 dw1, db1 = wgrad_for_params(w1, b1, x, pp_to_f32(dt_pp), 1, 1, ctx.has_b[0])
         if not t_done:
             plane_pool.put(t_pp, (main,))
-            if du_pp is not None:
-                plane_pool.put(du_pp, (main,))
+            plane_pool.put(du_pp, (main,))
         if not dt_done:
             plane_pool.put(dt_pp, (main,))
             if x_pp is not None:
@@ -1690,7 +1631,7 @@ def attention_tail(u, skip, fc1_w, fc2_w, w7, wc, bc, emit_pp=False):
     if _tail_eval_ok(u):
         _require_gpu(u, 'attention_tail')
         return _tail_forward_eval(u, skip, fc1_w, fc2_w, w7, wc, bc)
-    emit = bool(emit_pp and _X_PP and _PP_RAB and get_conv_math() == 'bf16x3' and u.is_cuda)
+    emit = bool(emit_pp and _X_PP and get_conv_math() == 'bf16x3' and u.is_cuda)
     out = _AttentionTail.apply(u, skip, fc1_w, fc2_w, w7, wc, bc, _carry_commit(skip), emit)
     pp, _state.last_out_pp = getattr(_state, 'last_out_pp', None), None
     if pp is not None:

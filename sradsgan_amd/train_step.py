@@ -87,16 +87,15 @@ class TrainStep:
         self.grad_sync = grad_sync                       # dp.GradSync or None
         self.use_graph = use_graph
         self.reuse_d_fake = reuse_d_fake
-        self.overlap_wgrad = overlap_wgrad = overlap_wgrad and os.environ.get('SRHIP_OVERLAP_WGRAD', '1') == '1'     # A/B knob
-        self.overlap_d_step = overlap_d_step and os.environ.get('SRHIP_OVERLAP_D', '1') == '1'
+        self.overlap_wgrad = overlap_wgrad
+        self.overlap_d_step = overlap_d_step
         if self.overlap_d_step and hasattr(torch.autograd.graph, 'set_warn_on_accumulate_grad_stream_mismatch'):
             # D's parameters are used on both streams by design; the engine orders their AccumulateGrad nodes itself
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         dev = self.arena_G.flat_p.device
         shared = _side_streams(dev) if (overlap_wgrad and dev.type == 'cuda') else (None, None)
         self._wgrad_stream = (wgrad_stream or shared[0]) if (overlap_wgrad and dev.type == 'cuda') else None
-        d_default = torch.cuda.Stream(device=dev, priority=-1) if os.environ.get('SRHIP_D_PRIO') == '1' else shared[1]   # knob: D stream at high priority
-        self._d_stream = (d_stream or d_default) if (overlap_wgrad and dev.type == 'cuda' and os.environ.get('SRHIP_D_STREAM', '1') == '1') else None
+        self._d_stream = (d_stream or shared[1]) if (overlap_wgrad and dev.type == 'cuda') else None
         self._bns = [m for m in self.D.modules() if isinstance(m, torch.nn.BatchNorm2d)]
         # weight gradients of one shape launched together (consecutive RABs): 1 = every conv on its own (A/B knob)
         self.wgrad_group = max(1, min(4, int(os.environ.get('SRHIP_WGRAD_GROUP', '2'))))
@@ -111,12 +110,10 @@ class TrainStep:
         self._d_params = self.arena_D.params
         if dev.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
             ops.plane_pool.release_all()                 # the previous model's padded-plane buffers (other geometries) go back to the allocator
-        self._g_parts, self._g_rest = self._plan_g_parts(int(os.environ.get('SRHIP_DP_PARTS', '3')))
+        self._g_parts, self._g_rest = self._plan_g_parts(3)
         self._parts_armed = False
         self._parts_sent = set()
         self._main = None
-        if grad_sync is not None and grad_sync.active and dev.type == 'cuda' and os.environ.get('SRHIP_DP_EAGER_INIT') == '1':
-            grad_sync.init_rccl(dev)                     # experiment only: see _compute_onewalk for when the communicator is created
         for k, grp in self._part_groups:
             grp.register_forward_hook(self._make_part_hook(k))
         for p in self.F.parameters():
@@ -147,7 +144,7 @@ class TrainStep:
 
     def _compute(self, imgs_lr, imgs_hr, alpha):
         if (self.reuse_d_fake and self.use_gp and self.overlap_wgrad and self.overlap_d_step and self._wgrad_stream is not None
-                and self._d_stream is not None and os.environ.get('SRHIP_D_ONEWALK', '1') == '1'):
+                and self._d_stream is not None):
             return self._compute_onewalk(imgs_lr, imgs_hr, alpha)
         if self.reuse_d_fake:
             return self._compute_shared(imgs_lr, imgs_hr, alpha)
@@ -317,9 +314,9 @@ class TrainStep:
         self._parts_sent = set()
         # The parts are armed from the SECOND iteration on: the first one hands both arenas over whole, from this thread, after the
         # backward -- that is where the communicator, its rendezvous and the comm stream come into being (GradSync.init_rccl inside
-        # start()), AFTER the step's three compute streams have been used and own their hardware queues.  Created before them (round 6
-        # tried it in TrainStep.__init__, to keep the rendezvous off autograd's device thread) the high-priority comm stream takes a
-        # queue the compute streams then share: 69.6 instead of 48.2 ms per step (profiles/r06_step_ab.txt).
+        # start()), AFTER the step's three compute streams have been used and own their hardware queues.  Created before them (measured
+        # in round 6 from TrainStep.__init__, to keep the rendezvous off autograd's device thread; removed) the high-priority comm stream
+        # takes a queue the compute streams then share: 69.6 instead of 48.2 ms per step (profiles/r06_step_ab.txt).
         self._parts_armed = (bool(self._g_parts) and gs is not None and gs.active and not self._capturing and not gs.host_sync
                              and (gs._rccl_ready or not self.arena_G.flat_g.is_cuda))
         self._set_d_grad(True)
@@ -399,7 +396,14 @@ class TrainStep:
         D(gen_hr.detach()) of the D step (:877) see the same input and the same weights, so one graph
         serves both -- the G-step backward walks it for d/d(gen_hr) only, the D-step backward for
         d/d(theta_D) only.  The running statistics of BatchNorm receive the update of the skipped forward
-        at the position the reference applies it (after D(real))."""
+        at the position the reference applies it (after D(real)).
+
+        Two host orders are left here (a three-stream step WITH the gradient penalty takes _compute_onewalk):
+          * the reference order -- G step, then D step, in program order -- without the D stream (overlap_wgrad=False: on one
+            stream, what tests/test_graph_gpu.py compares the others against; overlap_d_step=False: weight gradients and VGG(real)
+            on the weight-gradient stream);
+          * the three-stream order without the penalty (use_gp=False, the trainer with `gp` off): D's real pass on the D stream
+            before the generator's backward, then D's backward term by term."""
         G, D, F = self.G, self.D, self.F
         g_params, d_params = self.arena_G.params, self.arena_D.params
         self._set_d_grad(True)
@@ -417,9 +421,6 @@ class TrainStep:
         gen_hr = G(imgs_lr)
         self._mark('G fwd done')
         pixel = ops.l1_mean(gen_hr, imgs_hr)
-        early = os.environ.get('SRHIP_LATE_JOIN', '1') != '1' and side is not None     # A/B knob (old order)
-        if early:
-            _join_side(torch.cuda.current_stream(), side)
         fake_feat = F(gen_hr)
         stash = []
         for bn in self._bns:
@@ -455,68 +456,29 @@ class TrainStep:
             return loss_D, gp, terms, fake
 
         if side is not None and self.overlap_d_step:
-            # The discriminator's real / interpolate passes (incl. the first-order backward of the penalty) depend
-            # on gen_hr and D's weights only, not on the generator's backward: enqueue them on the side stream
-            # BEFORE the generator's backward so the two chains run concurrently on the GPU.  autograd replays every
-            # node on the stream of its forward, so their double backward stays on the side stream too.
+            # use_gp is False here (with the penalty this configuration takes _compute_onewalk).  The discriminator's real pass
+            # depends on gen_hr and D's weights only, not on the generator's backward: enqueue it on the D stream BEFORE the
+            # generator's backward so the two chains run concurrently on the GPU.  autograd replays every node on the stream
+            # of its forward, so its backward stays on the D stream too.
             main = torch.cuda.current_stream()
-            dside = self._d_stream if self._d_stream is not None else side   # third stream: the D passes beside G's dgrads (main) and the wgrads (side)
+            dside = self._d_stream                  # third stream: the D passes beside G's dgrads (main) and the wgrads (side)
             self._mark('fwd done (VGG, D(gen), losses)')
-            late = os.environ.get('SRHIP_D_LATE', '0') == '1'               # A/B knob, off by default
-            if late:
-                # Alternative HOST order: the generator's backward first, the D passes second (the D stream waits only for a
-                # forward-done event, so its kernels still run beside the generator's backward).  It removes a 6.6 ms dry
-                # spell of the main stream when the host is slow (under rocprofv3) and times the same at full host speed --
-                # but with the gradient exchange active it is 19 % SLOWER (74.0 vs 62.8 ms, single-rank communicator):
-                # the RCCL enqueue in _exchange_start('G') holds the host until the generator's backward has run, and in
-                # this order the D passes are not enqueued yet at that point.  Hence the D passes go first.
-                fwd_done = torch.cuda.Event()
-                fwd_done.record(main)
-                with ops.backward_scope(skip_params=d_params):    # no discriminator wgrads in the G step (:857 -> :865)
-                    torch.autograd.backward(loss_G, inputs=g_params, retain_graph=True)
-                self._exchange_start('G')                         # G's gradients travel under the whole D step
-                self._mark('G bwd done (main)')
-                self._mark('G wgrads done (wgrad stream)', side)
-                dside.wait_event(fwd_done)                        # gen_hr, d_gen and running-stat update #1 are in
-            else:
-                dside.wait_stream(main)
+            dside.wait_stream(main)
             self._mark('D passes begin (D stream)', dside)
-            early = self.use_gp and os.environ.get('SRHIP_D_EARLY', '1') == '1' and not late
             with torch.cuda.stream(dside):
                 loss_D, gp, terms, fake = d_forward()
-                stop = (gen_hr,) + ((self._interp,) if self.use_gp else ())      # (gradient_penalty sets _interp)
                 self._mark('D passes + GP first order done (D stream)', dside)
-                if early:
-                    # The real pass and the penalty live entirely on the D stream and do not depend on the generator's
-                    # backward: walk them HERE, with the D stream as the calling stream.  (Called from the main stream after
-                    # the generator's backward, the root gradient of each term is produced at that point of the MAIN
-                    # stream's queue, so the D stream sat idle from ~27 ms to ~48 ms of a 60 ms step and its serial
-                    # data-gradient / BatchNorm chain became a 10 - 15 ms tail, tools/step_timeline.py.)  Their weight-gradient
-                    # kernels run in line on the D stream -- the weight-gradient stream is one queue in host order, and
-                    # these would block the generator's weight gradients behind kernels that wait for the D stream.
-                    with ops.direct_param_grads(None), ops.backward_scope(stop_at=stop):
-                        self._backward_terms([terms[0], terms[2]], d_params)
-                    self._mark('D bwd of the real + penalty terms done (D stream)', dside)
             for t in (gen_hr, d_gen, alpha):
                 t.record_stream(dside)
-            if not late:
-                with ops.backward_scope(skip_params=d_params):
-                    torch.autograd.backward(loss_G, inputs=g_params, retain_graph=True)
-                self._exchange_start('G')
-                self._mark('G bwd done (main)')
-            if early:
-                # D's arena: the fake term's contributions (weight gradients on the weight-gradient stream, BatchNorm's in line
-                # on the main stream) after the D stream's
-                side.wait_stream(dside)
-                main.wait_stream(dside)
-                with ops.backward_scope(stop_at=stop):
-                    self._backward_terms([terms[1]], d_params)
-            else:
-                with ops.backward_scope(stop_at=stop):           # d/d(gen_hr) is not needed any more
-                    for t in terms:                              # real (D stream), fake (main), penalty (D stream): one
-                        self._backward_terms([t], d_params)      # after the other -- they add into the same arena slots
-                        main.wait_stream(dside)
-                        dside.wait_stream(main)
+            with ops.backward_scope(skip_params=d_params):    # no discriminator wgrads in the G step (:857 -> :865)
+                torch.autograd.backward(loss_G, inputs=g_params, retain_graph=True)
+            self._exchange_start('G')                         # G's gradients travel under the whole D step
+            self._mark('G bwd done (main)')
+            with ops.backward_scope(stop_at=(gen_hr,)):           # d/d(gen_hr) is not needed any more
+                for t in terms:                              # real (D stream), fake (main): one
+                    self._backward_terms([t], d_params)      # after the other -- they add into the same arena slots
+                    main.wait_stream(dside)
+                    dside.wait_stream(main)
             self._mark('D bwd done (main)')
             self._mark('D bwd done (D stream)', dside)
             self._mark('wgrads done (wgrad stream)', side)

@@ -5,8 +5,6 @@ device->host->PIL->numpy round trip.  Metrics follow the reference bit for bit w
 (scikit-image 0.15 algorithm, parity unpinned: skimage is not vendored by the reference).  LPIPS is not
 reproduced (its AlexNet weights are a download)."""
 import ctypes
-import math
-import os
 
 import torch
 
@@ -33,15 +31,6 @@ def quantized_metrics(sr, hr, scale):
     _hip.check(lib.srhip_quant_sse(_p(sr), _p(hr), _p(part), n, c * h * w, st), 'quant_sse')
     spart = torch.empty(n, nb, device=sr.device, dtype=torch.float64)
     _hip.check(lib.srhip_ssim_u8(_p(sr), _p(hr), _p(spart), n, h, w, c, st), 'ssim_u8')
-    if os.environ.get('SRHIP_METRIC_FINISH', '1') != '1':                  # A/B knob: the scalar tail as ~22 element-wise torch launches (rounds 2-4)
-        sums = part.sum(1).to(torch.float64)
-        count = float(c * h * w)
-        mse = sums[:, 0] / count
-        psnr = torch.where(mse > 0, 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(1e-300)), torch.full_like(mse, math.inf))
-        mean_gt = sums[:, 1] / count
-        ergas = 100.0 * torch.sqrt(mse / (mean_gt * mean_gt) / c) / scale
-        ssim = spart.sum(1) / float((h - 6) * (w - 6) * c)
-        return dict(mse=mse, psnr=psnr, ssim=ssim, ergas=ergas)
     out = torch.empty(4, n, device=sr.device, dtype=torch.float64)          # rows: mse, psnr, ssim, ergas (one launch for the scalar tail)
     _hip.check(lib.srhip_metric_finish(_p(part), _p(spart), _p(out), n, h, w, c, float(scale), st), 'metric_finish')
     return dict(mse=out[0], psnr=out[1], ssim=out[2], ergas=out[3])

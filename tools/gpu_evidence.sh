@@ -30,4 +30,3 @@ rm -rf $E/step/*.db
 BENCH_FORCE_DIST=1 timeout 300 python tools/step_timeline.py 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Host\|^Librccl\|amdgpu.ids" > $E/step_timeline_forced_single_rank_rccl.txt; tail -22 $E/step_timeline_forced_single_rank_rccl.txt
 timeout 300 python tools/step_timeline.py 2>&1 | grep -v amdgpu.ids > $E/step_timeline.txt
 timeout 300 python tools/time_d_convs.py 2>&1 | grep -v amdgpu.ids > $E/d_convs.txt
-bash tools/gpu_r6_traffic.sh > $E/traffic.log 2>&1; cp $R/gpurun_out/r6traffic/table.txt $E/step_traffic.txt; head -5 $E/step_traffic.txt
