@@ -13,6 +13,7 @@ import ctypes
 import os
 import threading
 import weakref
+from typing import NamedTuple
 
 import torch
 from torch.autograd import Function
@@ -25,20 +26,14 @@ CL = torch.channels_last
 class _State:
     # a plain global, not threading.local: autograd runs Function.backward on its own device thread
     skip_param_grads = False
-    direct_grads = False
-    wgrad_stream = None             # side HIP stream for weight-gradient kernels (direct_param_grads mode only)
+    wgrads = None                   # the _WgradQueue of the running direct_param_grads() context (None outside one)
     skip_ids = frozenset()          # id()s of parameters whose gradients the current backward must not produce
     stop_ids = frozenset()          # data_ptr()s of tensors the current backward must not propagate into
     capturing = False               # a stream capture is being recorded (TrainStep._capture): side-stream forks go through torch events
-    wgrad_group = 1                 # weight gradients of one shape launched together (srhip_conv2d_wgrad_multi); 1 = off
-    pending = None                  # shape key -> [(x, dy, gw, gb, stride, pad)] waiting for partners (direct_param_grads mode)
-    held = None                     # gradients kept referenced until the backward ends, see _passed_through
     last_out_pp = None              # _RabBlock.forward -> rab_block(): the output's padded planes (emit_pp)
     carry = None                    # token -> [gradients stashed for a block input by its other consumers] (carry_open)
     carry_expect = None             # token -> number of consumers that committed to stash at forward time
     carry_token = 0
-    wgrad_seq = 0                   # weight-gradient requests so far (the age of a pending launch, _age_pending)
-    ready_pairs = None              # complete flat-kernel launches waiting for their slot behind a conv1 data gradient (_WGRAD_SLOTS)
 
 
 _state = _State()
@@ -85,17 +80,15 @@ def direct_param_grads(side_stream=None, group=1):
     them: one wgrad launch per conv instead of wgrad + one `grad += new` launch per parameter
     (~600 tiny launches per step).  Only valid when every such parameter already owns a dense .grad
     and nobody asks autograd for these gradients explicitly (TrainStep guarantees both)."""
-    prev = (_state.direct_grads, _state.wgrad_stream, _state.wgrad_group, _state.pending, _state.held, _state.ready_pairs)
-    _state.direct_grads, _state.wgrad_stream = True, side_stream
-    _state.wgrad_group, _state.pending, _state.held, _state.ready_pairs = (group if side_stream is not None else 1), {}, [], []
+    prev, _state.wgrads = _state.wgrads, _WgradQueue(side_stream, group)
     try:
         yield
         flush_pending_wgrads()
-        if _state.pending:                             # before the restore below wipes the evidence
+        if _state.wgrads.pending:                      # before the restore below wipes the evidence
             raise RuntimeError('direct_param_grads: %d grouped weight gradient(s) still waiting for a partner after the flush'
-                               % len(_state.pending))
+                               % len(_state.wgrads.pending))
     finally:
-        _state.direct_grads, _state.wgrad_stream, _state.wgrad_group, _state.pending, _state.held, _state.ready_pairs = prev
+        _state.wgrads = prev
 
 
 _HOLD = int(os.environ.get('SRHIP_HOLD', '1'))     # 1: passed-through gradients (default); 2: every side-stream operand; 0: off (test knob)
@@ -108,8 +101,8 @@ def _hold_for_side(side, *tensors):
     profiles/r04_step_ab_small_changes.txt) and protects against graph shapes the model does not have -- a gradient that one
     producer hands to several consumers (torch's AddBackward, ops._SumN) is shared until the last of them has run, and the
     trunk's bus gradient is held by the head convs' buffers until the end of the backward."""
-    if _HOLD >= 2 and _state.held is not None:
-        _state.held.extend(t for t in tensors if t is not None)
+    if _HOLD >= 2 and _state.wgrads is not None:
+        _state.wgrads.held.extend(t for t in tensors if t is not None)
 
 
 def _passed_through(g):
@@ -123,8 +116,9 @@ def _passed_through(g):
     (tests/test_model_gpu.py: the first-step test after two pool streams, and the lagging-side-stream test).  With a second
     reference alive until the backward ends the engine allocates the sum instead, which is what it does for every gradient
     that is not aliased (12 + a few tensors of 24 MB per step)."""
-    if _HOLD and _state.wgrad_stream is not None and _state.held is not None and g is not None:
-        _state.held.append(g)
+    q = _state.wgrads
+    if _HOLD and q is not None and q.side is not None and g is not None:
+        q.held.append(g)
     return g
 
 
@@ -181,7 +175,7 @@ def _carry_take(token):
 
 def _grad_slot(p):
     """The buffer to accumulate into, or None when direct accumulation is off / impossible for p."""
-    if not _state.direct_grads or p is None or not p.requires_grad:
+    if _state.wgrads is None or p is None or not p.requires_grad:
         return None
     g = p.grad
     if g is None or not g.is_contiguous() or g.dtype != torch.float32 or g.device != p.device:
@@ -482,18 +476,28 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride, pad, residual=None, actmask=None, s
 _SIDE_WS = {}
 
 
-def _side_workspace(nbytes, device, stream):
-    """One persistent split-K workspace per side stream: the kernels of one stream run in order, so they can share it, and a
+def _wgrad_workspace(nbytes, device, stream=None):
+    """(split-K workspace, raw stream handle) of a weight-gradient launch.  On the current stream (stream=None): a fresh buffer.
+    On a side stream: ONE persistent buffer per stream -- the kernels of one stream run in order, so they can share it, and a
     buffer that is never freed needs no record_stream (a per-call buffer allocated on the launching stream and used on the
     side stream would)."""
+    need = (max(int(nbytes), 4) + 3) // 4
+    if stream is None:
+        return torch.empty(need, device=device, dtype=torch.float32), _stream()
     key = (device.index, stream.cuda_stream)
     ws = _SIDE_WS.get(key)
-    need = (max(int(nbytes), 4) + 3) // 4
     if ws is None or ws.numel() < need:
         if ws is not None:
             ws.record_stream(stream)                     # kernels already enqueued may still use the old buffer
         ws = _SIDE_WS[key] = torch.empty(max(need, 1 << 20), device=device, dtype=torch.float32)
-    return ws
+    return ws, ctypes.c_void_p(stream.cuda_stream)
+
+
+def _wgrad_tables(items):
+    """ctypes pointer tables (x, dy, dw, db) of a grouped launch: items are tuples or _Wgrad records, operands first."""
+    tab = ctypes.c_void_p * len(items)
+    cols = zip(*[(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None) for x, dy, dw, db, *_ in items])
+    return [tab(*col) for col in cols]
 
 
 def conv2d_wgrad_raw(x, dy, w_shape, stride, pad, with_bias=False, xrowscale=None, xchanscale=None, out=None, on_stream=None):
@@ -506,25 +510,14 @@ def conv2d_wgrad_raw(x, dy, w_shape, stride, pad, with_bias=False, xrowscale=Non
     n, cin, h, wd = x.shape
     cout, _, kh, kw = w_shape
     lib = _hip.lib()
-    nbytes = lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad)
-    if on_stream is not None:
-        ws = _side_workspace(nbytes, x.device, on_stream)
-        dw, db = out
-        _hip.check(lib.srhip_conv2d_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(xrowscale), _p(xchanscale), 1, _p(ws),
-                                          ws.numel() * 4, n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout,
-                                          ctypes.c_void_p(on_stream.cuda_stream)), 'conv2d_wgrad')
-        return dw, db
-    ws = torch.empty((max(nbytes, 4) + 3) // 4, device=x.device, dtype=torch.float32)
+    ws, st = _wgrad_workspace(lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad), x.device, on_stream)
     if out is None:
         dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
         db = torch.empty(cout, device=x.device, dtype=torch.float32) if with_bias else None
-        acc = 0
     else:
         dw, db = out
-        acc = 1
-    _hip.check(lib.srhip_conv2d_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(xrowscale), _p(xchanscale), acc, _p(ws),
-                                      ws.numel() * 4, n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout, _stream()),
-               'conv2d_wgrad')
+    _hip.check(lib.srhip_conv2d_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(xrowscale), _p(xchanscale), int(out is not None), _p(ws),
+                                      ws.numel() * 4, n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout, st), 'conv2d_wgrad')
     return dw, db
 
 
@@ -545,24 +538,13 @@ def _fork_side(side, handles=None):
 def conv2d_wgrad_multi_raw(items, on_stream=None):
     """items: [(x, dy, dw_buf, db_buf or None, stride, pad)] -- 2..4 weight gradients of ONE shape, accumulated into their
     buffers by one grouped launch (srhip_conv2d_wgrad_multi) on `on_stream` (default: the current stream)."""
-    x0, dy0, dw0, _, stride, pad = items[0]
+    x0, dy0, dw0, _, stride, pad, *_ = items[0]
     n, cin, h, wd = x0.shape
     cout, _, kh, kw = dw0.shape
     lib = _hip.lib()
-    k = len(items)
-    tab = ctypes.c_void_p * k
-    xs = tab(*[it[0].data_ptr() for it in items])
-    dys = tab(*[it[1].data_ptr() for it in items])
-    dws = tab(*[it[2].data_ptr() for it in items])
-    dbs = tab(*[(it[3].data_ptr() if it[3] is not None else None) for it in items])
-    nbytes = lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad)
-    if on_stream is not None:
-        ws = _side_workspace(nbytes, x0.device, on_stream)
-        st = ctypes.c_void_p(on_stream.cuda_stream)
-    else:
-        ws = torch.empty((max(nbytes, 4) + 3) // 4, device=x0.device, dtype=torch.float32)
-        st = _stream()
-    _hip.check(lib.srhip_conv2d_wgrad_multi(k, xs, dys, dws, dbs, 1, _p(ws), ws.numel() * 4, n, h, wd, cin, cout, kh, kw,
+    xs, dys, dws, dbs = _wgrad_tables(items)
+    ws, st = _wgrad_workspace(lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad), x0.device, on_stream)
+    _hip.check(lib.srhip_conv2d_wgrad_multi(len(items), xs, dys, dws, dbs, 1, _p(ws), ws.numel() * 4, n, h, wd, cin, cout, kh, kw,
                                            stride, pad, cin, cout, st), 'conv2d_wgrad_multi')
 
 
@@ -690,31 +672,21 @@ def conv2d_dgrad_pp_raw(dy, w, residual=None, actmask=None, slope=0.0, out_pp=No
 def conv2d_wgrad_pp_raw(items, accumulate=True, on_stream=None):
     """items: [(x, dy, dw_buf, db_buf or None)] -- 1..4 weight gradients of ONE 3x3 stride-1 pad-1 shape by one launch of the flat
     kernels (srhip_conv2d_wgrad_pp): x and / or dy are PP objects (padded planes), an operand that is not is fp32 NHWC."""
-    x0, dy0, dw0, _ = items[0]
+    x0, dy0, dw0, *_ = items[0]
     cout, cin = dw0.shape[0], dw0.shape[1]
     n, _, h, wd = x0.shape
     lib = _hip.lib()
     xpp, ypp = int(isinstance(x0, PP)), int(isinstance(dy0, PP))
-    for it in items[1:]:
-        if int(isinstance(it[0], PP)) != xpp or int(isinstance(it[1], PP)) != ypp:
+    for x, dy, *_ in items[1:]:
+        if int(isinstance(x, PP)) != xpp or int(isinstance(dy, PP)) != ypp:
             raise RuntimeError('conv2d_wgrad_pp: the convolutions of one launch must share their operand formats (planes / fp32)')
     mask = lib.srhip_conv2d_wgrad_pp_ok(n, h, wd, cin, cout)
     want = 4 if (xpp and ypp) else 1 if ypp else 2 if xpp else 0
     if not (mask & want):
         raise RuntimeError('conv2d_wgrad_pp: shape %s -> %d not served with these operand formats (served mask %d)' % (tuple(x0.shape), cout, mask))
     k = len(items)
-    tab = ctypes.c_void_p * k
-    xs = tab(*[it[0].data_ptr() for it in items])
-    dys = tab(*[it[1].data_ptr() for it in items])
-    dws = tab(*[it[2].data_ptr() for it in items])
-    dbs = tab(*[(it[3].data_ptr() if it[3] is not None else None) for it in items])
-    nbytes = lib.srhip_conv2d_wgrad_pp_workspace(k, xpp, ypp, n, h, wd, cin, cout)
-    if on_stream is not None:
-        ws = _side_workspace(nbytes, dw0.device, on_stream)
-        st = ctypes.c_void_p(on_stream.cuda_stream)
-    else:
-        ws = torch.empty((max(nbytes, 4) + 3) // 4, device=dw0.device, dtype=torch.float32)
-        st = _stream()
+    xs, dys, dws, dbs = _wgrad_tables(items)
+    ws, st = _wgrad_workspace(lib.srhip_conv2d_wgrad_pp_workspace(k, xpp, ypp, n, h, wd, cin, cout), dw0.device, on_stream)
     _hip.check(lib.srhip_conv2d_wgrad_pp(k, xs, dys, xpp, ypp, dws, dbs, 1 if accumulate else 0, _p(ws), ws.numel() * 4, n, h, wd, cin, cout,
                                         cout if xpp else cin, st), 'conv2d_wgrad_pp')
 
@@ -807,236 +779,235 @@ def _to_planes(t, device):
     return pp_from_f32(t, out=pp)
 
 
-def _launch_wgrad_pp(items, side):
-    """items: [(x, dy, gw, gb, release)] of one shape: fp32 operands are converted to planes (a pp_from_f32 pass of the 64-channel
-    operand: in-step +0.4 % over the kernel's own in-place split, profiles/r05_wgrad_flat.txt) and the flat kernel runs, all on `side`
-    (None: the current stream); pooled buffers go back to the pool with an event of that stream."""
-    main = torch.cuda.current_stream()
-    run_on = side if side is not None else main
-    with torch.cuda.stream(run_on):
-        conv = []
-        launch = []
-        for x, dy, gw, gb, release in items:
-            xo, dyo = x, dy
-            if not isinstance(x, PP):
-                xo = _to_planes(x, gw.device)
-                conv.append(xo)
-            if not isinstance(dy, PP):
-                dyo = _to_planes(dy, gw.device)
-                conv.append(dyo)
-            launch.append((xo, dyo, gw, gb))
-        conv2d_wgrad_pp_raw(launch, accumulate=True, on_stream=side)
-        for pp in conv:
-            plane_pool.put(pp, (run_on,))
-        for x, dy, gw, gb, release in items:
-            for pp in release:
-                plane_pool.put(pp, (run_on,) if side is None else (run_on, main))
-    if side is not None:
-        for x, dy, gw, gb, release in items:
-            for t in (x, dy):
-                if not isinstance(t, PP):
-                    t.record_stream(side)
-            if not isinstance(dy, PP):
-                _hold_for_side(side, dy)
-
-
-def wgrad_pp_for_params(w, b, x, dy, want_b, release=()):
-    """Weight (+ bias) gradient of a 3x3 stride-1 pad-1 conv whose 256-channel operand is a PP (the other fp32 NHWC), accumulated into
-    the parameters' gradient slots by the flat kernel -- in pairs on the weight-gradient stream like wgrad_for_params.  `release`:
-    pooled PP buffers that go back to the pool once the launch is enqueued.  Returns False when direct accumulation is not possible
-    (the caller converts and takes the fp32 path)."""
-    gw = _grad_slot(w)
-    gb = _grad_slot(b) if (want_b and b is not None) else None
-    if gw is None or (want_b and b is not None and gb is None):
-        return False
-    side = _state.wgrad_stream
-    _age_pending()
-    item = (x, dy, gw, gb, tuple(release))
-    if side is None:
-        _launch_wgrad_pp([item], None)
-        return True
-    if _state.wgrad_group > 1:
-        key = ('pp', tuple(x.shape), w.shape[0], gb is not None, isinstance(x, PP), isinstance(dy, PP))   # one launch = one operand format
-        q = _state.pending.setdefault(key, [])
-        q.append(item + (_stream().value, _state.wgrad_seq))
-        if len(q) >= _PP_GROUP:
-            if _WGRAD_SLOTS and _state.ready_pairs is not None and not _state.capturing:
-                _state.ready_pairs.append(_state.pending.pop(key))      # complete: goes out at the next slot (release_ready_pair)
-            else:
-                _flush_key(key)
-        return True
-    _fork_side(side)
-    _launch_wgrad_pp([item], side)
-    return True
-
-
-def _flush_key(key):
-    items = _state.pending.pop(key, None)
-    if not items:
-        return
-    side = _state.wgrad_stream
-    if key[0] == 'pp':
-        _fork_side(side, [it[5] for it in items])
-        _launch_wgrad_pp([it[:5] for it in items], side)
-        return
-    _fork_side(side, [it[6] for it in items])
-    items = [it[:6] for it in items]              # at most the step's group size: a queue goes out the moment it is that long
-    if len(items) == 1:
-        x, dy, gw, gb, stride, pad = items[0]
-        if _state.capturing:
-            with torch.cuda.stream(side):
-                conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb))
-        else:
-            conv2d_wgrad_raw(x, dy, tuple(gw.shape), stride, pad, gb is not None, out=(gw, gb), on_stream=side)
-    elif _state.capturing:
-        with torch.cuda.stream(side):
-            conv2d_wgrad_multi_raw(items)
-    else:
-        conv2d_wgrad_multi_raw(items, on_stream=side)
-    for it in items:
-        it[0].record_stream(side)
-        it[1].record_stream(side)
-        _hold_for_side(side, it[1])
-
-
 _WGRAD_MAX_AGE = 14    # weight-gradient calls a launch may wait for a partner
-
-
-def _age_pending():
-    """Called at every weight-gradient request: a pending launch whose partner has not shown up within _WGRAD_MAX_AGE further requests
-    goes out alone.  The RAB pairs meet within 4-5 requests; shapes that occur ONCE per backward (the up-sampler's conv at 54^2 and at
-    108^2) used to wait for the flush at the END of the generator's backward and then ran, alone on the chip, for 0.5 ms after the
-    main stream had finished (`tools/step_tail.py`, profiles/r05_step_tail_before.txt)."""
-    _state.wgrad_seq += 1
-    if not _state.pending:
-        return
-    for key in [k for k, q in _state.pending.items() if q and _state.wgrad_seq - q[0][-1] > _WGRAD_MAX_AGE]:
-        _flush_key(key)
-
-
 # RAB weight gradients of one shape per flat-kernel launch.  Round 6: 3 -- a ResGroup's three RABs -- instead of pairs: the launch keeps one
 # block per CU, so every convolution gets a third instead of half of the split-K splits (28 instead of 42): a third fewer partial tiles written and
 # reduced, and the launches line up with the group boundaries the exchange's parts are cut at.  +0.5 % same-box (profiles/r06_step_ab.txt; 4: the same)
 _PP_GROUP = 3
-_WGRAD_SLOTS = os.environ.get('SRHIP_WGRAD_SLOTS', '0') == '1'     # experiment, OFF: see release_ready_pair (kernel-level effect as predicted, step unchanged)
+_WGRAD_SLOTS = os.environ.get('SRHIP_WGRAD_SLOTS', '0') == '1'     # experiment, OFF: see _WgradQueue.release (kernel-level effect as predicted, step unchanged)
 
 
-def _launch_ready(items):
-    side = _state.wgrad_stream
-    _fork_side(side, [it[5] for it in items])
-    _launch_wgrad_pp([it[:5] for it in items], side)
+class _Wgrad(NamedTuple):
+    """One requested weight gradient: gw += wgrad(x, dy), gb += colsum(dy)."""
+    x: object                       # operands: fp32 NHWC tensors, on the plane path also PP
+    dy: object
+    gw: torch.Tensor                # the parameters' gradient slots (gb: None = no bias gradient)
+    gb: object
+    stride: int
+    pad: int
+    release: tuple                  # pooled PP buffers that go back to the pool once the launch is enqueued
+    producer: object                # raw handle of the stream the request came from: the one that produced the operands
+    seq: int                        # the queue's request number at the request (the age of a pending launch, _WgradQueue.tick)
+
+
+class _WgradQueue:
+    """The weight gradients of one direct_param_grads() context: WHEN each is launched, BEHIND WHICH streams, and WHAT is kept alive until
+    it has run.  Nothing reads a weight gradient before the optimiser, so they run on a side stream (`side`; None: the current stream,
+    at once) beside the data gradients: the partially filled last wave of each data-gradient kernel and of each weight-gradient kernel
+    overlap, and same-parameter accumulations stay ordered (one side stream).  Requests of one shape wait in `pending` for partners
+    (`group` > 1) and go out in one launch."""
+
+    def __init__(self, side, group):
+        self.side = side
+        self.capturing = _state.capturing               # (a stream capture wraps the whole context: TrainStep._capture)
+        self.group = group if side is not None else 1   # weight gradients of one shape launched together (srhip_conv2d_wgrad_multi); 1 = off
+        self.slots = _WGRAD_SLOTS and not self.capturing   # complete plane launches wait for their slot (release)
+        self.pending = {}                               # shape key -> [_Wgrad] waiting for partners
+        self.ready = []                                 # complete plane launches waiting for their slot
+        self.held = []                                  # gradients kept referenced until the backward ends, see _passed_through
+        self.seq = 0                                    # weight-gradient requests so far
+
+    def job(self, x, dy, gw, gb, stride=1, pad=1, release=()):
+        return _Wgrad(x, dy, gw, gb, stride, pad, release, _stream().value, self.seq)
+
+    def run(self, jobs, launch, extra=(), by_handle=False):
+        """The ONE place that runs something on the side stream: orders it behind the current stream and the jobs' producers, calls
+        launch(on) -- on = the side stream when the launch takes it by raw handle (by_handle: no stream context, ~150 launches per step;
+        not inside a capture, where the workspace must come from the capture's pool), else None = torch's current stream, which is
+        then the side stream --, marks the fp32 operands (the jobs' x / dy and `extra`) as in use on it and holds the jobs' gradients
+        (_hold_for_side).  Without a side stream: launch(None), at once."""
+        side = self.side
+        if side is None:
+            launch(None)
+            return
+        _fork_side(side, [j.producer for j in jobs])
+        if by_handle and not self.capturing:
+            launch(side)
+        else:
+            with torch.cuda.stream(side):
+                launch(None)
+        for t in [t for j in jobs for t in (j.x, j.dy)] + list(extra):
+            if t is not None and not isinstance(t, PP):
+                t.record_stream(side)
+        _hold_for_side(side, *[j.dy for j in jobs if not isinstance(j.dy, PP)])
+
+    def run_fp32(self, jobs):
+        """One launch for fp32 jobs of one shape (at most the step's group size: a pending list goes out the moment it is that long)."""
+        def launch(on):
+            if len(jobs) == 1:
+                j, = jobs
+                conv2d_wgrad_raw(j.x, j.dy, tuple(j.gw.shape), j.stride, j.pad, j.gb is not None, out=(j.gw, j.gb), on_stream=on)
+            else:
+                conv2d_wgrad_multi_raw(jobs, on_stream=on)
+        self.run(jobs, launch, by_handle=True)
+
+    def run_planes(self, jobs):
+        """One launch of the flat kernel for plane jobs of one shape: fp32 operands are converted to planes (a pp_from_f32 pass of the
+        64-channel operand: in-step +0.4 % over the kernel's own in-place split, profiles/r05_wgrad_flat.txt) and the flat kernel runs, all
+        on the side stream (None: the current stream); pooled buffers go back to the pool with an event of that stream."""
+        main = torch.cuda.current_stream()
+        side = self.side
+        run_on = side if side is not None else main
+
+        def launch(_):
+            conv, items = [], []
+            for j in jobs:
+                xo, dyo = j.x, j.dy
+                if not isinstance(xo, PP):
+                    xo = _to_planes(xo, j.gw.device)
+                    conv.append(xo)
+                if not isinstance(dyo, PP):
+                    dyo = _to_planes(dyo, j.gw.device)
+                    conv.append(dyo)
+                items.append((xo, dyo, j.gw, j.gb))
+            conv2d_wgrad_pp_raw(items, accumulate=True, on_stream=side)
+            for pp in conv:
+                plane_pool.put(pp, (run_on,))
+            for j in jobs:
+                for pp in j.release:
+                    plane_pool.put(pp, (run_on,) if side is None else (run_on, main))
+        self.run(jobs, launch)
+
+    def tick(self):
+        """Called at every weight-gradient request: a pending launch whose partner has not shown up within _WGRAD_MAX_AGE further requests
+        goes out alone.  The RAB pairs meet within 4-5 requests; shapes that occur ONCE per backward (the up-sampler's conv at 54^2 and at
+        108^2) used to wait for the flush at the END of the generator's backward and then ran, alone on the chip, for 0.5 ms after the
+        main stream had finished (`tools/step_tail.py`, profiles/r05_step_tail_before.txt)."""
+        self.seq += 1
+        for key in [k for k, q in self.pending.items() if q and self.seq - q[0].seq > _WGRAD_MAX_AGE]:
+            self.flush(key)
+
+    def add(self, key, job, group):
+        """`job` waits under `key` for partners of its shape; the `group`-th completes the launch."""
+        q = self.pending.setdefault(key, [])
+        q.append(job)
+        if len(q) >= group:
+            self.complete(key)
+
+    def complete(self, key):
+        if self.slots and key[0] == 'pp':
+            self.ready.append(self.pending.pop(key))      # goes out at the next slot (release)
+        else:
+            self.flush(key)
+
+    def flush(self, key):
+        jobs = self.pending.pop(key, None)
+        if jobs:
+            (self.run_planes if key[0] == 'pp' else self.run_fp32)(jobs)
+
+    def flush_all(self):
+        self.release(len(self.ready))
+        for key in list(self.pending):
+            self.flush(key)
+
+    def release(self, n=1):
+        """Round 6: WHEN a complete pair of RAB weight gradients starts.  The 8-wave flat kernel holds one block on every CU for ~150 us
+        (2 x 170 of the 512 registers per SIMD lane) and leaves room for ONE block of a main-stream conv beside it.  The 128-wide conv
+        kernels live with that (12 MFMAs per barrier and wave: 87 us in the step against 79 alone); the 64-wide one -- conv1's data gradient,
+        256 -> 64, 6 MFMAs per barrier -- does not: 149 us in the step against 77 alone, 36 times per step on the main stream's chain
+        (profiles/r06_step_eager_kernel_stats.txt).  And the round-5 request order put the two exactly on top of each other: conv2's
+        weight gradient was requested between conv2's and conv1's data gradient, so a pair that completed there started the moment
+        conv1's data gradient did.  Now complete pairs wait in `ready` and ONE goes out right after every conv1 data gradient
+        has been enqueued (_RabBlock._backward_planes): it runs beside the next block's attention tail (streaming passes) and conv2 data
+        gradient (128-wide) -- ~210 us, room for one pair -- and is mostly done when the next conv1 data gradient starts.  Same kernels,
+        same accumulation order per parameter: bit-identical.
+        MEASURED (profiles/r06_step_ab.txt): conv1's data gradient 147.7 -> 91.6 us in the step, exactly as intended -- and the step does not
+        move (668.8 / 672.3 / 671.1 against 669.5 / 672.1 / 671.0 img/s): the tail's 1x1 data gradient (39 -> 48 us), the split-K reduces
+        (23 -> 31) and the 1x1 weight gradients (35 -> 40) take up what it gives back.  During the backward the chip's throughput is the limit,
+        not any kernel's place in a queue.  Kept as an option (SRHIP_WGRAD_SLOTS=1), off by default."""
+        for jobs in self.ready[:n]:
+            self.run_planes(jobs)
+        del self.ready[:n]
 
 
 def release_ready_pair(n=1):
-    """Round 6: WHEN a complete pair of RAB weight gradients starts.  The 8-wave flat kernel holds one block on every CU for ~150 us
-    (2 x 170 of the 512 registers per SIMD lane) and leaves room for ONE block of a main-stream conv beside it.  The 128-wide conv
-    kernels live with that (12 MFMAs per barrier and wave: 87 us in the step against 79 alone); the 64-wide one -- conv1's data gradient,
-    256 -> 64, 6 MFMAs per barrier -- does not: 149 us in the step against 77 alone, 36 times per step on the main stream's chain
-    (profiles/r06_step_eager_kernel_stats.txt).  And the round-5 request order put the two exactly on top of each other: conv2's
-    weight gradient was requested between conv2's and conv1's data gradient, so a pair that completed there started the moment
-    conv1's data gradient did.  Now complete pairs wait in _state.ready_pairs and ONE goes out right after every conv1 data gradient
-    has been enqueued (_RabBlock._backward_planes): it runs beside the next block's attention tail (streaming passes) and conv2 data
-    gradient (128-wide) -- ~210 us, room for one pair -- and is mostly done when the next conv1 data gradient starts.  Same kernels,
-    same accumulation order per parameter: bit-identical.
-    MEASURED (profiles/r06_step_ab.txt): conv1's data gradient 147.7 -> 91.6 us in the step, exactly as intended -- and the step does not
-    move (668.8 / 672.3 / 671.1 against 669.5 / 672.1 / 671.0 img/s): the tail's 1x1 data gradient (39 -> 48 us), the split-K reduces
-    (23 -> 31) and the 1x1 weight gradients (35 -> 40) take up what it gives back.  During the backward the chip's throughput is the limit,
-    not any kernel's place in a queue.  Kept as an option (SRHIP_WGRAD_SLOTS=1), off by default."""
-    q = _state.ready_pairs
-    while q and n > 0:
-        _launch_ready(q.pop(0))
-        n -= 1
+    """One complete launch of RAB weight gradients that waits for its slot goes out now (_WgradQueue.release, SRHIP_WGRAD_SLOTS=1)."""
+    if _state.wgrads is not None:
+        _state.wgrads.release(n)
 
 
 def flush_pending_pp():
     """The RAB weight gradients of the flat kernel that are still waiting for partners go out now (end of a ResGroup's backward)."""
-    if _state.pending:
-        for key in [k for k in _state.pending if k[0] == 'pp']:
-            if _WGRAD_SLOTS and _state.ready_pairs is not None and not _state.capturing:
-                _state.ready_pairs.append(_state.pending.pop(key))
-            else:
-                _flush_key(key)
+    q = _state.wgrads
+    if q is not None:
+        for key in [k for k in q.pending if k[0] == 'pp']:
+            q.complete(key)
 
 
 def flush_pending_wgrads():
     """Launches every weight gradient that is still waiting for a partner of its shape (and every complete pair that is waiting for
     its slot).  Called wherever something is about to order itself behind "all weight gradients so far": the exchange, the joins of
     the step, the end of direct_param_grads()."""
-    if _state.ready_pairs:
-        release_ready_pair(len(_state.ready_pairs))
-    if _state.pending:
-        for key in list(_state.pending):
-            _flush_key(key)
+    if _state.wgrads is not None:
+        _state.wgrads.flush_all()
+
+
+def wgrad_pp_for_params(w, b, x, dy, want_b, release=()):
+    """Weight (+ bias) gradient of a 3x3 stride-1 pad-1 conv whose 256-channel operand is a PP (the other fp32 NHWC), accumulated into
+    the parameters' gradient slots by the flat kernel -- in groups on the weight-gradient stream like wgrad_for_params.  `release`:
+    pooled PP buffers that go back to the pool once the launch is enqueued.  Returns False when direct accumulation is not possible
+    (the caller converts and takes the fp32 path)."""
+    gw = _grad_slot(w)
+    gb = _grad_slot(b) if (want_b and b is not None) else None
+    if gw is None or (want_b and b is not None and gb is None):
+        return False
+    q = _state.wgrads
+    q.tick()
+    job = q.job(x, dy, gw, gb, release=tuple(release))
+    if q.group > 1:
+        q.add(('pp', tuple(x.shape), w.shape[0], gb is not None, isinstance(x, PP), isinstance(dy, PP)), job, _PP_GROUP)   # one launch = one operand format
+    else:
+        q.run_planes([job])
+    return True
 
 
 def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscale=None):
     """(dw, db) to return to autograd for parameters (w, b).  In direct_param_grads() mode the kernel
-    accumulates into w.grad / b.grad and this returns (None, None)."""
+    accumulates into w.grad / b.grad, on the weight-gradient stream (_WgradQueue), and this returns (None, None)."""
     cout, cin, kh, kw = w.shape
     gw = _grad_slot(w)
     gb = _grad_slot(b) if (want_b and b is not None) else None
-    if gw is not None and (not want_b or gb is not None) and \
-            _hip.lib().srhip_conv2d_wgrad_can_accumulate(cin, cout, kh, kw):
-        side = _state.wgrad_stream
-        if side is None:
-            conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, out=(gw, gb))
-            return None, None
-        _age_pending()
-        # Weight gradients are off the critical path of backward (nothing reads them before the optimiser):
-        # run them on a side stream so the partially filled last wave of each data-gradient kernel and of
-        # each wgrad kernel overlap.  Same-parameter accumulations stay ordered (one side stream).
-        x, dy = nhwc(x), nhwc(dy)
-        if (_state.wgrad_group > 1 and xrowscale is None and xchanscale is None and (gb is not None or not want_b)
-                and _hip.lib().srhip_conv2d_wgrad_multi_ok(x.shape[0], x.shape[2], x.shape[3], cin, cout, kh, kw, stride, pad)
-                >= _state.wgrad_group):
+    if gw is None or (want_b and gb is None):
+        return conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
+    q = _state.wgrads
+    x, dy = nhwc(x), nhwc(dy)
+    lib = _hip.lib()
+    if lib.srhip_conv2d_wgrad_can_accumulate(cin, cout, kh, kw):
+        q.tick()
+        job = q.job(x, dy, gw, gb, stride, pad)
+        if (q.group > 1 and xrowscale is None and xchanscale is None
+                and lib.srhip_conv2d_wgrad_multi_ok(x.shape[0], x.shape[2], x.shape[3], cin, cout, kh, kw, stride, pad) >= q.group):
             # nothing reads a weight gradient before the optimiser: wait for a partner of the same shape (the next RAB's) and
             # launch them together -- one full wave of blocks serves both with half the split-K partials each
-            key = (tuple(x.shape), cout, stride, pad, gb is not None)
-            q = _state.pending.setdefault(key, [])
-            q.append((x, dy, gw, gb, stride, pad, _stream().value, _state.wgrad_seq))     # + the stream that produced the operands, + the request number
-            if len(q) >= _state.wgrad_group:
-                _flush_key(key)
-            return None, None
-        if _state.capturing:
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, out=(gw, gb))
+            q.add((tuple(x.shape), cout, stride, pad, gb is not None), job, q.group)
         else:
             # one C call forks the side stream behind the current one (event ring inside the library) and the kernel is
             # launched on it by handle: no torch Event, no stream context, no per-call workspace (~150 launches per step)
-            _hip.check(_hip.lib().srhip_stream_fork(_stream(), ctypes.c_void_p(side.cuda_stream)), 'stream_fork')
-            conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, out=(gw, gb), on_stream=side)
-        for t in (x, dy, xrowscale, xchanscale):
-            if t is not None:
-                t.record_stream(side)
-        _hold_for_side(side, dy)
+            q.run([job], lambda on: conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, out=(gw, gb), on_stream=on),
+                  extra=(xrowscale, xchanscale), by_handle=True)
         return None, None
-    if gw is not None and (not want_b or gb is not None):
-        # Shapes the accumulating kernel does not take (the 3- and 2-channel convs, the 64 -> 3 tail conv): add in program order
-        # here rather than through autograd's AccumulateGrad, whose order among several contributions to one parameter
-        # follows per-thread node counters (tests/test_graph_gpu.py) -- and, like the other weight gradients, on the side
-        # stream: the 3 -> 64 head convs' gradients (0.2 - 0.3 ms each at 216 x 216) sat in the discriminator's serial chain
-        side = _state.wgrad_stream
-        if side is None:
-            dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
-            gw.add_(dw)
-            if db is not None:
-                gb.add_(db)
-            return None, None
-        x, dy = nhwc(x), nhwc(dy)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
-            gw.add_(dw)
-            if db is not None:
-                gb.add_(db)
-        for t in (x, dy, xrowscale, xchanscale):
-            if t is not None:
-                t.record_stream(side)
-        _hold_for_side(side, dy)
-        return None, None
-    return conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
+
+    # Shapes the accumulating kernel does not take (the 3- and 2-channel convs, the 64 -> 3 tail conv): add in program order
+    # here rather than through autograd's AccumulateGrad, whose order among several contributions to one parameter
+    # follows per-thread node counters (tests/test_graph_gpu.py) -- and, like the other weight gradients, on the side
+    # stream: the 3 -> 64 head convs' gradients (0.2 - 0.3 ms each at 216 x 216) sat in the discriminator's serial chain
+    def launch(_):
+        dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
+        gw.add_(dw)
+        if db is not None:
+            gb.add_(db)
+    q.run([q.job(x, dy, gw, gb, stride, pad)], launch, extra=(xrowscale, xchanscale))
+    return None, None
 
 
 def _wgrad_act_direct(w, b, x, dy, y, slope, stride, pad):
@@ -1051,24 +1022,17 @@ def _wgrad_act_direct(w, b, x, dy, y, slope, stride, pad):
     if not lib.srhip_conv2d_wgrad_act_ok(n, h, wd, cin, cout, kh, kw, stride, pad):
         return False
     x, dy, y = nhwc(x), nhwc(dy), nhwc(y)
-    side = _state.wgrad_stream
-    cur = torch.cuda.current_stream()
-    run_on = side if side is not None else cur
-    if side is not None:
-        side.wait_stream(cur)
-    with torch.cuda.stream(run_on):
-        nbytes = lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad)
-        ws = torch.empty((max(nbytes, 4) + 3) // 4, device=x.device, dtype=torch.float32)
+
+    def launch(_):
+        ws, st = _wgrad_workspace(lib.srhip_conv2d_wgrad_workspace(n, h, wd, cin, cout, kh, kw, stride, pad), x.device)
         dw = torch.empty(tuple(w.shape), device=x.device, dtype=torch.float32)
         db = torch.empty(cout, device=x.device, dtype=torch.float32)
         _hip.check(lib.srhip_conv2d_wgrad_act(_p(x), _p(dy), _p(y), float(slope), _p(dw), _p(db), _p(ws), ws.numel() * 4,
-                                              n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout, _stream()), 'conv2d_wgrad_act')
+                                              n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout, st), 'conv2d_wgrad_act')
         gw.add_(dw)
         gb.add_(db)
-    if side is not None:
-        for t in (x, dy, y):
-            t.record_stream(side)
-        _hold_for_side(side, dy)
+    q = _state.wgrads
+    q.run([q.job(x, dy, gw, gb, stride, pad)], launch, extra=(y,))
     return True
 
 
@@ -1169,7 +1133,7 @@ class _ConvFwd(Function):
         skip = _skip_param_grads(w)
         need_dx = ctx.needs_input_grad[0] and x.data_ptr() not in _state.stop_ids
         if ctx.slope is not None and not need_dx and not skip and ctx.needs_input_grad[1] and ctx.has_bias and \
-                ctx.needs_input_grad[2] and _state.direct_grads and not torch.is_grad_enabled() and \
+                ctx.needs_input_grad[2] and _state.wgrads is not None and not torch.is_grad_enabled() and \
                 _wgrad_act_direct(w, b, x, dy, y, ctx.slope, ctx.stride, ctx.pad):
             # head conv of the discriminator in the D step: only its parameter gradients are wanted, and the kernel applies the
             # activation's backward while it reads dy -- no lrelu-backward pass over the 382 MB gradient in the serial chain
@@ -1178,7 +1142,7 @@ class _ConvFwd(Function):
         dx = _ConvDgrad.apply(g, w, tuple(x.shape), ctx.stride, ctx.pad) if need_dx else None
         dw = db = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2] and not skip
-        if ctx.needs_input_grad[1] and not skip and _state.direct_grads and not torch.is_grad_enabled():
+        if ctx.needs_input_grad[1] and not skip and _state.wgrads is not None and not torch.is_grad_enabled():
             dw, db = wgrad_for_params(w, b, x, g, ctx.stride, ctx.pad, want_b)
         elif ctx.needs_input_grad[1] and not skip:
             dw, db = _ConvWgrad.apply(x, g, tuple(w.shape), ctx.stride, ctx.pad, want_b)
@@ -1203,7 +1167,7 @@ class _ConvDgrad(Function):
         skip = _skip_param_grads(w)
         d_dy = _ConvFwd.apply(ddx, w, None, None, ctx.stride, ctx.pad, None, True) if ctx.needs_input_grad[0] else None
         d_w = None
-        if ctx.needs_input_grad[1] and not skip and _state.direct_grads and not torch.is_grad_enabled():
+        if ctx.needs_input_grad[1] and not skip and _state.wgrads is not None and not torch.is_grad_enabled():
             d_w, _ = wgrad_for_params(w, None, ddx, dy, ctx.stride, ctx.pad, False)   # same stream/order as every other wgrad of w
         elif ctx.needs_input_grad[1] and not skip:
             d_w, _ = _ConvWgrad.apply(ddx, dy, tuple(w.shape), ctx.stride, ctx.pad, False)
@@ -1555,16 +1519,20 @@ class _RabBlock(Function):
         dw2 = db2 = dw1 = db1 = None
         main = torch.cuda.current_stream()
         t_done = dt_done = False
-        slots = _WGRAD_SLOTS and _state.ready_pairs is not None
-        if slots:                                         # conv1's data gradient FIRST, then one waiting pair of weight gradients (release_ready_pair)
-            dx = conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None
-            release_ready_pair(1)
+        q = _state.wgrads
+        slots = q is not None and q.slots
+
+        def conv1_dgrad():                                # + skip gradient (+ the input's stashed gradients)
+            return conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None
+        if slots:                                         # conv1's data gradient FIRST, then one waiting launch of weight gradients (_WgradQueue.release)
+            dx = conv1_dgrad()
+            q.release(1)
         if not skip:
             t_done = wgrad_pp_for_params(w2, b2, t_pp, du_pp, ctx.has_b[1], release=(t_pp, du_pp))
             if not t_done:                                # autograd wants the gradients returned: the fp32 path on converted operands
                 dw2, db2 = wgrad_for_params(w2, b2, pp_to_f32(t_pp), pp_to_f32(du_pp), 1, 1, ctx.has_b[1])
         if not slots:
-            dx = conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None   # + skip gradient (+ the input's stashed gradients)
+            dx = conv1_dgrad()
         if not skip:
             dt_done = wgrad_pp_for_params(w1, b1, x_pp if x_pp is not None else x, dt_pp, ctx.has_b[0],
                                           release=(dt_pp,) if x_pp is None else (dt_pp, x_pp))
@@ -1578,7 +1546,7 @@ class _RabBlock(Function):
             if x_pp is not None:
                 plane_pool.put(x_pp, (main,))
         if slots and x_pp is None:                        # the trunk's first block = the backward's last: no further slot will come
-            release_ready_pair(len(_state.ready_pairs))
+            q.release(len(q.ready))
         if ctx.group_first:
             flush_pending_pp()                            # a launch never straddles ResGroups: what the exchange's group-boundary flush finds is the same with and without it
         return dx, dw1, db1, dw2, db2, dfc1, dfc2, dw7, dwc, dbc, None, None, None, None
@@ -2410,7 +2378,7 @@ class _ConvPool(Function):
         dx = _ConvDgrad.apply(dy, w, tuple(x.shape), 1, 1) if ctx.needs_input_grad[0] else None
         dw = db = None
         want_b = b is not None and ctx.needs_input_grad[2] and not skip
-        if ctx.needs_input_grad[1] and not skip and _state.direct_grads and not torch.is_grad_enabled():
+        if ctx.needs_input_grad[1] and not skip and _state.wgrads is not None and not torch.is_grad_enabled():
             dw, db = wgrad_for_params(w, b, x, dy, 1, 1, want_b)
         elif ctx.needs_input_grad[1] and not skip:
             dw, db = _ConvWgrad.apply(x, dy, tuple(w.shape), 1, 1, want_b)
