@@ -64,7 +64,8 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *         Later in ABI 14, additive only: the channel attention with biases (srhip_ca_mlp_fwd_bias, srhip_ca_mlp_bwd_bias) for
  *         RCAN; HAT's window-transformer passes (srhip_hat_*: LayerNorm, GELU, window attention, channel attention at any
  *         C <= 128 and the block combine).  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
- *         declared symbol by name when it loads the library, so a library without them fails at load time. */
+ *         declared symbol by name when it loads the library, so a library without them fails at load time.
+ *         The LPIPS metric's passes (srhip_lpips_*, srhip_maxpool3x3s2_fwd) joined the same way: additive, version 14. */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -666,6 +667,26 @@ int srhip_ssim_u8(const float* a, const float* b, double* partial, int n, int h,
  * ssim, ergas (utils.py:923-962) */
 int srhip_metric_finish(const unsigned long long* sse_partial, const double* ssim_partial, double* out, int n, int h, int w, int c,
                         double scale, void* stream);
+
+/* ---- LPIPS, the fourth validation metric (sradsgan.py:561 `PerceptualLoss('net-lin', 'alex')`, called per image at :1125-1132 and
+ *      :1326-1332; utils/PerceptualSimilarity/__init__.py:26-44, networks_basic.py:64-105, pretrained_networks.py:57-96).  Forward only.
+ * lpips_stem: the scaling layer and AlexNet features[0:2] in one pass.  x [m][h][w][3] in [0,1] (normalize != 0: x = 2x - 1 first,
+ *   __init__.py:36-38) -> (x - shift) / scale per channel (networks_basic.py:101-105) on in-image taps only -- the conv pads with zeros
+ *   in the scaled space -- then conv 3->64 k11 s4 p2 + bias + ReLU in exact fp32 in every conv-math mode.
+ *   w_hwio: the weight as [11][11][3][64] (ky, kx, ci, co); y [m][ho][wo][64], ho = (h + 4 - 11) / 4 + 1.  Needs h, w >= 7.
+ * maxpool3x3s2_fwd: nn.MaxPool2d(3, 2) of features[2] / [5]: floor mode, no padding, ho = (h - 3) / 2 + 1; C % 4 == 0, h, w >= 3.
+ * lpips_head: one tap.  f [m][h][w][c] holds the features of all images; pairs = int32 [npairs][2] on the device, indices into m
+ *   (the caller checks them); w [c] = the tap's lin weights.  Per pixel: f / (sqrt(sum_c f^2) + 1e-10) for both images, then
+ *   sum_c w[c] * (difference)^2 (networks_basic.py:70-78, __init__.py:42-44).  partial: double [npairs][srhip_lpips_blocks()] pixel
+ *   sums, fixed reduction order, no atomics.  C % 4 == 0.
+ * lpips_finish: partial = double [ntaps][npairs][srhip_lpips_blocks()], tap_pixels = host array of h * w per tap (read during the
+ *   call) -> out[npairs] = sum over taps of (pixel sum / pixels): spatial_average and the sum of the layers (:83-87).               */
+int srhip_lpips_stem(const float* x, const float* w_hwio, const float* bias, float* y, int m, int h, int w, int normalize, void* stream);
+int srhip_maxpool3x3s2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
+int srhip_lpips_blocks(void);
+int srhip_lpips_head(const float* f, const int* pairs, const float* w, double* partial, int m, int npairs, int h, int wd, int c,
+                     void* stream);
+int srhip_lpips_finish(const double* partial, const long* tap_pixels, int ntaps, int npairs, double* out, void* stream);
 
 /* ---- torch.optim.Adam (sradsgan.py:724-725, step at :858 and :887) over a flat fp32 arena, fused
  *      with the discriminator's weight clip `p.data.clamp_(-c, c)` (:891-892; clip <= 0: none).

@@ -165,6 +165,11 @@ SIGNATURES = {
     'srhip_quant_sse': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'srhip_ssim_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'srhip_metric_finish': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
+    'srhip_lpips_stem': (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    'srhip_maxpool3x3s2_fwd': (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_lpips_blocks': (_i, []),
+    'srhip_lpips_head': (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    'srhip_lpips_finish': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     'srhip_hat_ln_parts': (_i, [_l]),
     'srhip_hat_ln_fwd': (_i, [_vp] * 6 + [_l, _vp]),
     'srhip_hat_ln_bwd': (_i, [_vp] * 10 + [_l, _vp]),

@@ -2145,6 +2145,60 @@ def max_pool2x2_raw(x):
     return y
 
 
+def max_pool3x3s2_raw(x):
+    """nn.MaxPool2d(kernel_size=3, stride=2) (AlexNet features[2] / [5]): floor mode, no padding.  Forward only."""
+    _require_gpu(x, 'max_pool3x3s2')
+    x = nhwc(x)
+    n, c, h, w = x.shape
+    if h < 3 or w < 3:
+        raise ValueError('max_pool3x3s2: needs H, W >= 3, got %d x %d' % (h, w))
+    y = empty_nhwc(n, c, (h - 3) // 2 + 1, (w - 3) // 2 + 1, x)
+    _hip.check(_hip.lib().srhip_maxpool3x3s2_fwd(_p(x), _p(y), n, h, w, c, _stream()), 'maxpool3x3s2_fwd')
+    return y
+
+
+def lpips_stem_raw(x, w_hwio, bias, normalize=True, out=None):
+    """Scaling layer + AlexNet conv1 + ReLU (srhip_lpips_stem).  x: [M,3,H,W]; w_hwio: the weight as a dense [11,11,3,64] tensor; out: an
+    NHWC [M,64,Ho,Wo] tensor (or a batch slice of one) to write into."""
+    _require_gpu(x, 'lpips_stem')
+    x = nhwc(x)
+    m, c, h, w = x.shape
+    if c != 3 or tuple(w_hwio.shape) != (11, 11, 3, 64) or not w_hwio.is_contiguous():
+        raise ValueError('lpips_stem: needs a 3-channel image and a dense [11, 11, 3, 64] weight')
+    if h < 7 or w < 7:
+        raise ValueError('lpips_stem: needs H, W >= 7, got %d x %d' % (h, w))
+    ho, wo = _out_hw(h, w, 11, 4, 2)
+    y = empty_nhwc(m, 64, ho, wo, x) if out is None else out
+    if tuple(y.shape) != (m, 64, ho, wo) or not y.is_contiguous(memory_format=CL):
+        raise ValueError('lpips_stem: out must be a dense NHWC %s tensor' % ((m, 64, ho, wo),))
+    _hip.check(_hip.lib().srhip_lpips_stem(_p(x), _p(w_hwio), _p(bias.detach().contiguous()), _p(y), m, h, w, int(bool(normalize)),
+                                           _stream()), 'lpips_stem')
+    return y
+
+
+def lpips_head_raw(f, pairs, w, partial):
+    """One tap of the LPIPS head (srhip_lpips_head).  f: [M,C,h,w] features; pairs: int32 [P,2] on the device (indices into M, checked by
+    the caller); w: [C]; partial: float64 [P, srhip_lpips_blocks()] that receives the pixel sums."""
+    _require_gpu(f, 'lpips_head')
+    f = nhwc(f)
+    m, c, h, wd = f.shape
+    npairs = pairs.shape[0]
+    if pairs.dtype != torch.int32 or not pairs.is_cuda or not pairs.is_contiguous() or w.numel() != c:
+        raise ValueError('lpips_head: pairs must be a dense int32 [P, 2] device tensor and w must have C elements')
+    _hip.check(_hip.lib().srhip_lpips_head(_p(f), _p(pairs), _p(w.detach().contiguous()), _p(partial), m, npairs, h, wd, c, _stream()),
+               'lpips_head')
+    return partial
+
+
+def lpips_finish_raw(partial, tap_pixels, out=None):
+    """partial: float64 [T,P,blocks]; tap_pixels: h * w of each tap -> float64 [P] = sum over taps of the pixel means."""
+    ntaps, npairs = partial.shape[0], partial.shape[1]
+    out = torch.empty(npairs, device=partial.device, dtype=torch.float64) if out is None else out
+    counts = (ctypes.c_long * ntaps)(*[int(v) for v in tap_pixels])
+    _hip.check(_hip.lib().srhip_lpips_finish(_p(partial), counts, ntaps, npairs, _p(out), _stream()), 'lpips_finish')
+    return out
+
+
 _POOL_IDX = os.environ.get('SRHIP_POOL_IDX', '1') == '1'        # A/B knob: 0 = the max-pool backward re-reads the pool's input
 
 

@@ -11,8 +11,11 @@ The data side: like the reference (`load_dataset`, sradsgan.py:643-656) the trai
 copied on their own HIP stream, and turned into (lr, hr, bc) on the device (sradsgan_amd.data.training_batch /
 test_batch, bit-exact with the reference's PIL transforms) instead of 16 PIL worker processes.  An injected iterable
 (`train_loader`, `test_loader`: the reference's own DataLoader tuples `(lr, hr, bc, paths)` or uint8 HR tiles
-`[N, H, W, 3]`) takes precedence.  Metrics are computed on the device (validate.py); LPIPS is not reproduced (AlexNet weights are a
-download): the lpips slots of the returned tuples and log lines carry NaN.  PNG panels are not written."""
+`[N, H, W, 3]`) takes precedence.  Metrics are computed on the device (validate.py).  LPIPS (sradsgan.py:561) is computed when it is
+configured: `args.lpips_alexnet` (a torchvision AlexNet state-dict file, the user's to supply) together with `args.lpips_lin` (the
+reference's utils/PerceptualSimilarity/weights/v0.1/alex.pth), or `set_lpips(model)` with a loaded sradsgan_amd.lpips.LPIPS.  Not
+configured, the lpips slots of the returned tuples and log lines carry NaN and the epoch control sees 10000.  PNG panels are not
+written."""
 import argparse
 import math
 import os
@@ -25,6 +28,7 @@ import torch
 from . import checkpoint as ckpt
 from . import data as sdata
 from . import dp
+from . import lpips as slpips
 from . import validate as sval
 from .model import Discriminator, FeatureExtractor, GeneratorResNet, ResGroup
 from .train_step import TrainStep
@@ -78,6 +82,11 @@ class SRADSGAN(object):
         self.pretrained_generator = getattr(args, 'pretrained_generator', None)      # chain training, see _build
         self.pretrained_discriminator = getattr(args, 'pretrained_discriminator', None)
         self.train_loader, self.test_loader = train_loader, test_loader
+        self.lpips = None
+        self.lpips_alexnet = getattr(args, 'lpips_alexnet', None)                    # state-dict paths, see set_lpips
+        self.lpips_lin = getattr(args, 'lpips_lin', None)
+        if bool(self.lpips_alexnet) != bool(self.lpips_lin):
+            raise ValueError('LPIPS needs both args.lpips_alexnet (torchvision AlexNet state dict) and args.lpips_lin (alex.pth)')
         # data parallel: one process per GPU under torch.distributed; replicas start identical (broadcast
         # from rank 0), gradients are averaged by TrainStep's GradSync, BatchNorm stays local, rank 0 owns files and
         # logs, validation results and with them every rollback decision are rank 0's
@@ -223,6 +232,19 @@ class SRADSGAN(object):
         return history
 
     # ------------------------------------------------------------------ validation -------------- #
+    def set_lpips(self, model):
+        """Use `model` (a loaded sradsgan_amd.lpips.LPIPS, or None to switch the metric off) as `self.lpips_metric` of the reference
+        (sradsgan.py:561)."""
+        self.lpips = None if model is None else model.to(self.device)
+
+    def _lpips_model(self):
+        if self.lpips is None and self.lpips_alexnet:
+            model = slpips.LPIPS()
+            model.load_torchvision_alexnet(torch.load(self.lpips_alexnet, map_location='cpu'))
+            model.load_lin(torch.load(self.lpips_lin, map_location='cpu'))
+            self.set_lpips(model)
+        return self.lpips
+
     def _evaluate_loader(self, generator, label, loader=None, totals=None):
         if loader is None:
             if self.test_loader is None:
@@ -230,15 +252,19 @@ class SRADSGAN(object):
             loader = self.test_loader
         sums = {k: 0.0 for k in ('bicubic_mse', 'bicubic_psnr', 'bicubic_ssim', 'bicubic_ergas', label + '_mse', label + '_psnr',
                                  label + '_ssim', label + '_ergas')}
+        lpips = self._lpips_model()
+        metrics = ('mse', 'psnr', 'ssim', 'ergas') + (() if lpips is None else ('lpips',))
+        if lpips is not None:
+            sums['bicubic_lpips'] = sums[label + '_lpips'] = 0.0
         img_num = 0
         was_training = generator.training
         generator.eval()                                                                         # :1288
         start = time.time()
         for item in loader:
             imgs_lr, imgs_hr, imgs_bc = self._batch(item, test=True)
-            out = sval.evaluate(generator, imgs_lr, imgs_hr, self.scale_factor, bicubic=imgs_bc)
+            out = sval.evaluate(generator, imgs_lr, imgs_hr, self.scale_factor, bicubic=imgs_bc, lpips=lpips)
             img_num += imgs_hr.size(0)
-            for k in ('mse', 'psnr', 'ssim', 'ergas'):
+            for k in metrics:
                 sums['bicubic_' + k] += float(out['bicubic'][k].sum())
                 sums[label + '_' + k] += float(out['sr'][k].sum())
         generator.train(was_training)
@@ -254,7 +280,7 @@ class SRADSGAN(object):
         for prefix in ('bicubic', label):                                                        # :1377-1390 key order
             for k in ('mse', 'psnr', 'ssim', 'ergas'):
                 rlt['%s_%s' % (prefix, k)] = avg['%s_%s' % (prefix, k)]
-            rlt['%s_lpips' % prefix] = float('nan')
+            rlt['%s_lpips' % prefix] = avg.get('%s_lpips' % prefix, float('nan'))
         if self.rank != 0:
             return
         os.makedirs(self.save_dir, exist_ok=True)
@@ -267,7 +293,7 @@ class SRADSGAN(object):
             self.load_epoch_model(epoch)
         avg, elapsed = self._evaluate_loader(self.generator, 'srcnn')
         self._log_val(epoch, avg, elapsed, 'srcnn')
-        return avg['srcnn_psnr'], avg['srcnn_ssim'], avg['srcnn_ergas'], float('nan')
+        return avg['srcnn_psnr'], avg['srcnn_ssim'], avg['srcnn_ergas'], avg.get('srcnn_lpips', float('nan'))
 
     def mfeNew_validate(self, epoch=100, modelpath=None):
         """sradsgan.py:1258-1391: fresh generator, optional `modelpath` (strict=False), same averages and log line
@@ -278,7 +304,8 @@ class SRADSGAN(object):
             ckpt._after_load()
         avg, elapsed = self._evaluate_loader(self.generator, self.eval_label)
         self._log_val(epoch, avg, elapsed, self.eval_label)
-        return avg[self.eval_label + '_psnr'], avg[self.eval_label + '_ssim'], avg[self.eval_label + '_ergas'], float('nan')
+        return (avg[self.eval_label + '_psnr'], avg[self.eval_label + '_ssim'], avg[self.eval_label + '_ergas'],
+                avg.get(self.eval_label + '_lpips', float('nan')))
 
     def mfeNew_validateByClass(self, epoch, save_img=False, modelpath=None):
         """sradsgan.py:1393-1601: the validation of mfeNew_validate once per class folder of the test set, one

@@ -2,8 +2,9 @@
 mfeNew_validate / validate loops (SRADSGAN/model/sradsgan.py:1258-1391, 1058-1194) without the per-image
 device->host->PIL->numpy round trip.  Metrics follow the reference bit for bit where it is integer work
 (uint8 quantisation with wrap, MSE, PSNR, ERGAS of utils/utils.py:923-962) and to fp64 roundoff for SSIM
-(scikit-image 0.15 algorithm, parity unpinned: skimage is not vendored by the reference).  LPIPS is not
-reproduced (its AlexNet weights are a download)."""
+(scikit-image 0.15 algorithm, parity unpinned: skimage is not vendored by the reference).  LPIPS (sradsgan.py:561,
+1125-1132, 1326-1332) is computed when the caller passes a loaded sradsgan_amd.lpips.LPIPS model; the pretrained AlexNet
+file it needs is the user's to supply, and without a model the metric is simply absent from the results."""
 import ctypes
 
 import torch
@@ -37,13 +38,22 @@ def quantized_metrics(sr, hr, scale):
 
 
 @torch.no_grad()
-def evaluate(generator, lr, hr, scale, bicubic=None):
+def evaluate(generator, lr, hr, scale, bicubic=None, lpips=None):
     """One validation batch: recon = G(lr) (sradsgan.py:1305), metrics of recon vs hr and -- when the
-    bicubic-upsampled input is given -- of bicubic vs hr (:1328-1331).  Returns per-image metric dicts."""
+    bicubic-upsampled input is given -- of bicubic vs hr (:1328-1331).  Returns per-image metric dicts.
+    lpips: an lpips.LPIPS model; then out['sr']['lpips'] (and out['bicubic']['lpips']) are float64 [N] of the unquantised
+    images (:1326-1332), the backbone running once over [recon; hr; bicubic]."""
     recon = generator(lr)
     out = {'recon': recon, 'sr': quantized_metrics(recon, hr, scale)}
     if bicubic is not None:
         out['bicubic'] = quantized_metrics(bicubic, hr, scale)
+    if lpips is not None:
+        n = hr.shape[0]
+        images = [hr, recon] + ([] if bicubic is None else [bicubic])
+        d = lpips.pairs(images, [(i, n + i) for i in range(n)] + ([] if bicubic is None else [(i, 2 * n + i) for i in range(n)]))
+        out['sr']['lpips'] = d[:n]
+        if bicubic is not None:
+            out['bicubic']['lpips'] = d[n:]
     return out
 
 
@@ -55,8 +65,8 @@ class GraphedEvaluator:
     Weights are read at replay time, so an evaluator stays valid across training steps as long as the parameter
     storage does not move (ParamArena guarantees that) and ops.repack_all() has run after the last update."""
 
-    def __init__(self, generator, scale, warmup=2):
-        self.generator, self.scale, self.warmup = generator, scale, warmup
+    def __init__(self, generator, scale, warmup=2, lpips=None):
+        self.generator, self.scale, self.warmup, self.lpips = generator, scale, warmup, lpips
         self._graphs = {}
 
     def _capture(self, key, lr, hr, bicubic):
@@ -65,11 +75,11 @@ class GraphedEvaluator:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # library / allocator / packed-weight warm-up outside the capture
             for _ in range(self.warmup):
-                evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'])
+                evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'])
+            out = evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips)
         self._graphs[key] = (graph, static, out)
 
     def __call__(self, lr, hr, bicubic=None):
