@@ -591,7 +591,7 @@ __global__ void tail_bwd_fix_kernel(float* __restrict__ du, const float* __restr
     const bf16x2_t l01 = {(__bf16)(d.x - __uint_as_float(uh01 << 16)), (__bf16)(d.y - __uint_as_float(uh01 & 0xffff0000u))};
     const bf16x2_t l23 = {(__bf16)(d.z - __uint_as_float(uh23 << 16)), (__bf16)(d.w - __uint_as_float(uh23 & 0xffff0000u))};
     // the two lanes of an octet trade halves: the even lane stores the octet's 8 hi halves, the odd lane its 8 lo halves, 16 bytes each
-    // (whole rows per store instruction; see epi_finish in conv_fast.hip)
+    // (whole rows per store instruction; see epi_finish in conv_fast_fprop.hip)
     const bool odd = (cq & 1) != 0;
     const unsigned ul01 = __builtin_bit_cast(unsigned, l01), ul23 = __builtin_bit_cast(unsigned, l23);
     const unsigned r0 = pair_swap(odd ? uh01 : ul01), r1 = pair_swap(odd ? uh23 : ul23);

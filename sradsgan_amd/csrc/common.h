@@ -9,6 +9,7 @@
 namespace srhip {
 
 void set_error(const char* fmt, ...);
+extern int g_conv_math;   // SRHIP_MATH_* arithmetic of the MFMA kernels (srhip_set_conv_math; defined in conv_fast_fprop.hip)
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();

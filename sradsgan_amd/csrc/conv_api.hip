@@ -1,5 +1,5 @@
 // C-ABI entry points of the convolution family (include/sradsgan_hip.h): argument checking and the
-// choice between the fast kernels (conv_fast.hip) and the generic implicit-GEMM (conv_igemm.hip).
+// choice between the fast kernels (conv_fast_fprop.hip, conv_wgrad_fast.hip) and the generic implicit-GEMM (conv_igemm.hip).
 // The choice depends only on the conv's static shape, so srhip_pack_weight and srhip_conv2d_* agree.
 #include "conv_internal.h"
 #include "conv_dev.h"
@@ -114,27 +114,6 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const PackEntry* __re
 }  // namespace srhip
 
 namespace srhip {
-extern int g_fast_cfg;
-extern int g_wgrad_cfg;
-extern int g_rowtap_addr;
-extern int g_rowtap_pipe;
-extern int g_patch_ks;
-extern int g_fast_dynlds;
-extern int g_fast_ablate;
-extern int g_conv_math;
-extern int g_sgam_cfg;
-extern int g_pers_grid;
-extern int g_pers_small;
-extern int g_pool_epi_any;
-extern int g_pers_abl;
-extern int g_phase_batch;
-extern int g_headconv_rows;
-}
-extern int g_tail_dbg;
-namespace srhip {
-}
-
-namespace srhip {
 // ---- in-step timing probe (srhip_probe_*): HIP-event pairs around the conv launches of ONE shape, on their launch stream ----
 struct Probe {
   int kind = 0, n = 0, h = 0, w = 0, cin = 0, cout = 0, cap = 0, count = 0;
@@ -197,87 +176,12 @@ int srhip_probe_read(float* ms, int* units, int cap) {
 
 /* tuning/experiment knobs; key 0 = fast conv tile configuration (0 = built-in heuristic) */
 int srhip_debug_set(int key, int value) {
-  if (key == 0) {
-    g_fast_cfg = value;
-    return SRHIP_OK;
-  }
-  if (key == 1) {
-    g_wgrad_cfg = value;
-    return SRHIP_OK;
-  }
-  if (key == 2) {
-    g_fast_dynlds = value;
-    return SRHIP_OK;
-  }
-  if (key == 3) {
-    g_fast_ablate = value;
-    return SRHIP_OK;
-  }
-  if (key == 4) {
-    g_sgam_cfg = value;
-    return SRHIP_OK;
-  }
-  if (key == 5) {
-    g_pers_grid = value;
-    return SRHIP_OK;
-  }
-  if (key == 6) {
-    g_pers_abl = value;
-    return SRHIP_OK;
-  }
-  if (key == 7) {
-    g_tail_dbg = value;
-    return SRHIP_OK;
-  }
-  if (key == 8) {
-    g_rowtap_addr = value;
-    return SRHIP_OK;
-  }
-  if (key == 9) {
-    g_rowtap_pipe = value;
-    return SRHIP_OK;
-  }
-  if (key == 10) {
-    g_patch_ks = value;
-    return SRHIP_OK;
-  }
-  if (key == 11) {
-    g_pers_small = value;
-    return SRHIP_OK;
-  }
-  if (key == 12) {
-    g_flat_blocks = value > 0 ? value : 768;
-    return SRHIP_OK;
-  }
-  if (key == 13) {
-    g_flat_abl = value;
-    return SRHIP_OK;
-  }
-  if (key == 14) {
-    g_flat_f32_k8 = value;
-    return SRHIP_OK;
-  }
-  if (key == 15) {
-    g_patch8 = value;
-    return SRHIP_OK;
-  }
-  if (key == 16) {
-    g_patch8_abl = value;
-    return SRHIP_OK;
-  }
-  if (key == 17) {
-    g_phase_batch = value;
-    return SRHIP_OK;
-  }
-  if (key == 18) {
-    g_headconv_rows = value;
-    return SRHIP_OK;
-  }
-  if (key == 19) {
-    g_pool_epi_any = value;
-    return SRHIP_OK;
-  }
-  return SRHIP_ERR_ARG;
+  static int* const knobs[] = {&g_fast_cfg,    &g_wgrad_cfg,  &g_fast_dynlds,  &g_fast_ablate,  &g_sgam_cfg,      &g_pers_grid,  &g_pers_abl,
+                               &g_tail_dbg,    &g_rowtap_addr, &g_rowtap_pipe, &g_patch_ks,     &g_pers_small,    &g_flat_blocks, &g_flat_abl,
+                               &g_flat_f32_k8, &g_patch8,     &g_patch8_abl,   &g_phase_batch,  &g_headconv_rows, &g_pool_epi_any};   // index = key (conv_dev.h)
+  if (key < 0 || key >= (int)(sizeof(knobs) / sizeof(knobs[0]))) return SRHIP_ERR_ARG;
+  *knobs[key] = (key == 12 && value <= 0) ? 768 : value;
+  return SRHIP_OK;
 }
 
 int srhip_set_conv_math(int mode) {
@@ -344,7 +248,7 @@ int srhip_conv2d_fwd(const float* x, const float* packed, const float* bias, con
 
 /* ABI 9: srhip_conv2d_fwd whose fp32 output y ALSO leaves as padded split-bf16 planes (y_pp, zeroed once by the caller): the
  * attention tail's 1x1 conv (sradsgan.py:262-274) hands the next RAB its input in both forms.  *served = 1 when the kernel that
- * took the launch wrote the planes (the row-group-epilogue kernels of conv_fast.hip), else 0: the caller converts y itself. */
+ * took the launch wrote the planes (the row-group-epilogue kernels of conv_fast_fprop.hip), else 0: the caller converts y itself. */
 int srhip_conv2d_fwd_dual(const float* x, const float* packed, const float* bias, const float* residual, const float* rowscale,
                           const float* chanscale, float* y, void* y_pp, int* served, int n, int h, int w, int cin, int cout, int kh,
                           int kw, int stride, int pad, int ldx, int ldy, int ldr, float slope, int flags, void* stream) {
@@ -496,7 +400,7 @@ int srhip_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, co
 }
 
 /* nprob (2..4) weight gradients of the SAME shape (stride-1 3x3, row-tap eligible, split-bf16 / half arithmetic) in one launch:
- * x[i], dy[i] -> dw[i] (+ db[i] when db and db[i] are non-NULL), written or accumulated into.  See WgradBatch in conv_fast.hip. */
+ * x[i], dy[i] -> dw[i] (+ db[i] when db and db[i] are non-NULL), written or accumulated into.  See WgradBatch in conv_wgrad_fast.hip. */
 int srhip_conv2d_wgrad_multi_ok(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad) {
   if (n <= 0 || h <= 0 || w <= 0 || !fast_wgrad_ok(cin, cout, kh, kw)) return 0;
   return fast_wgrad_multi_max(n, h, w, cin, cout, kh, kw, stride, pad);

@@ -1,5 +1,6 @@
-// Device-side helpers shared by the fast convolution translation units (conv_fast.hip, conv_patch_pers.hip):
-// geometry structs, the split-bf16 fragment arithmetic, LDS-DMA issue helpers and the patch-tile pixel map.
+// Shared by the fast convolution translation units (conv_fast_fprop.hip, conv_wgrad_fast.hip,
+// conv_patch_pers.hip, conv_patch8.hip): the debug knobs and the names of their values, geometry structs, the split-bf16
+// fragment arithmetic, LDS-DMA issue helpers and the patch-tile pixel map.
 #pragma once
 #include "conv_internal.h"
 
@@ -26,7 +27,7 @@ struct FastGeom {
   // [guard + N (H+1) (W+1) + tail] pixel rows of channels * 4 bytes (per 8 channels: 8 hi | 8 lo halves); Hs / Ws (Hd / Wd) stay the LOGICAL image size
   int src_pp = 0, dst_pp = 0, src_guard = 0, dst_guard = 0;
   unsigned src_plane_bytes = 0, dst_plane_bytes = 0;
-  // a SECOND destination: the fp32 output also as padded planes (the kernels with the row-group epilogue of conv_fast.hip only --
+  // a SECOND destination: the fp32 output also as padded planes (the kernels with the row-group epilogue of conv_fast_fprop.hip only --
   // the attention tail's 1x1 conv leaves the next block's input x in both forms); NULL: not wanted
   void* dst2_pp = nullptr;
   int dst2_guard = 0;
@@ -70,6 +71,91 @@ struct Dst2Request {                // rides beside ONE srhip_conv2d_fwd call (c
   int served = 0;
 };
 extern thread_local Dst2Request g_dst2_req;
+
+// ================================================================================================ //
+// Debug / experiment knobs: srhip_debug_set(key, value) (conv_api.hip holds the key table).  Every knob is DEFINED in the
+// file that owns it and declared here, once.
+// ================================================================================================ //
+}  // namespace srhip
+extern int g_tail_dbg;        // key 7  (attn_tail.hip): timing-only ablation bits of attn_tail_eval_kernel
+namespace srhip {
+// (the arithmetic mode g_conv_math is not a debug key -- srhip_set_conv_math -- and is read outside the conv files: common.h declares it)
+extern int g_fast_cfg;        // key 0  (conv_fast_fprop.hip): a FastCfg value
+extern int g_wgrad_cfg;       // key 1  (conv_wgrad_fast.hip): a WgradCfg value
+extern int g_fast_dynlds;     // key 2  (conv_fast_fprop.hip): extra dynamic LDS bytes per block = occupancy limiter
+extern int g_fast_ablate;     // key 3  (conv_fast_fprop.hip): FAST_ABL_* bits, OR-ed into FastGeom::flags of forward calls
+extern int g_sgam_cfg;        // key 4  (global_attn.hip)
+extern int g_pers_grid;       // key 5  (conv_patch_pers.hip): > 0 blocks of the persistent patch kernel, -1 never take it
+extern int g_pers_abl;        // key 6  (conv_patch_pers.hip)
+extern int g_rowtap_addr;     // key 8  (conv_wgrad_fast.hip)
+extern int g_rowtap_pipe;     // key 9  (conv_wgrad_fast.hip)
+extern int g_patch_ks;        // key 10 (conv_fast_fprop.hip)
+extern int g_pers_small;      // key 11 (conv_patch_pers.hip)
+extern int g_flat_blocks;     // key 12 (conv_wgrad_flat.hip): values <= 0 mean the default, 768
+extern int g_flat_abl;        // key 13 (conv_wgrad_flat.hip)
+extern int g_flat_f32_k8;     // key 14 (conv_wgrad_flat.hip)
+extern int g_patch8;          // key 15 (conv_patch8.hip)
+extern int g_patch8_abl;      // key 16 (conv_patch8.hip)
+extern int g_phase_batch;     // key 17 (conv_fast_fprop.hip)
+extern int g_headconv_rows;   // key 18 (conv_igemm.hip)
+extern int g_pool_epi_any;    // key 19 (conv_patch_pers.hip)
+
+// g_fast_cfg: which fprop / dgrad kernel choose_fprop_route (conv_fast_fprop.hip) may take.  0 is the heuristic; every other
+// value exists for A/B runs and for the tests that pin one kernel against another.
+enum FastCfg : int {
+  FAST_CFG_FORCE_PATCH = -2,   // the patch family at any launch size (the heuristic wants >= 256 tiles)
+  FAST_CFG_FORCE_DMA = -1,     // the LDS-DMA kernels at any problem size
+  FAST_CFG_AUTO = 0,
+  // 1..8: no LDS-DMA / patch kernel; above 32 destination channels the register-staged kernel with this tile, BM x BN (waves WM x WN), BK
+  FAST_CFG_REG_128x128_K32 = 1,   // 2 x 2; needs >= 128 destination channels and source channels % 32 == 0
+  FAST_CFG_REG_64x128 = 2,        // 1 x 4; >= 128 destination channels
+  FAST_CFG_REG_64x128_K32 = 3,    // 1 x 4; >= 128 destination channels, source channels % 32 == 0
+  FAST_CFG_REG_256x128 = 4,       // 4 x 2; >= 128 destination channels
+  FAST_CFG_REG_128x128 = 5,       // 2 x 2; >= 128 destination channels
+  FAST_CFG_REG_128x64_K32 = 6,    // 2 x 2; source channels % 32 == 0
+  FAST_CFG_REG_64x64 = 7,         // 2 x 2
+  FAST_CFG_REG_128x64_4x1_K32 = 8,   // 4 x 1; source channels % 32 == 0
+  FAST_CFG_REG_ONLY = 20,      // register-staged fp32-product kernels only: no VALU, 16-bit <= 32-channel, patch or LDS-DMA kernel
+  FAST_CFG_NO_PATCH = 21,      // the patch family off (its launches reach the LDS-DMA kernel through the heuristic)
+  FAST_CFG_NO_VALU = 22,       // narrow_conv_kernel and dot_conv_kernel off
+  FAST_CFG_PATCH_TO_DMA = 23,  // every launch the patch family would take goes to the (bit-identical) LDS-DMA kernel
+  FAST_CFG_PATCH_NARROW = 24,  // experiment: 64-wide N tiles of the patch family for every Cout (twice the blocks)
+};
+// the LDS-DMA and patch families are open to the heuristic values and to the two that only steer between them
+inline bool fast_cfg_allows_dma(int cfg) { return cfg < 1 || cfg == FAST_CFG_PATCH_TO_DMA || cfg == FAST_CFG_PATCH_NARROW; }
+
+// g_wgrad_cfg: which weight-gradient kernel and tile choose_wgrad_route / plan_fast_wgrad (conv_wgrad_fast.hip) take.
+// value % 10 picks the tile (1, 2); value >= 10 = the register-staged kernel where the LDS-DMA kernel would run, and 10..99 also
+// turn the row-tap kernel off; >= 100 = the row-tap kernel's split-K block target (the default is 768).
+enum WgradCfg : int {
+  WGRAD_CFG_AUTO = 0,
+  WGRAD_CFG_BN64 = 1,          // (% 10) N tile 64
+  WGRAD_CFG_BN128 = 2,         // (% 10) N tile 128
+  WGRAD_CFG_BK32 = 3,          // 32-pixel K chunks (exact fp32 only: fast_wgrad_dma_kernel<.., 32, 0>)
+  WGRAD_CFG_BK32_BN64 = 4,     // the same with N tile 64
+  WGRAD_CFG_TILE256 = 5,       // 256-wide tiles: 256 x 64 for Cout % 256 == 0, 64 x 256 for Cout == 64
+  WGRAD_CFG_SCALAR_REDUCE_GENERIC = 6,   // scalar split-K reduce kernel (16 sub-sums from 256 splits on), generic kernel for the 1x1 tail
+  WGRAD_CFG_NO_ROWTAP = 7,     // the row-tap kernel off
+  WGRAD_CFG_SCALAR_REDUCE = 8, // scalar split-K reduce kernels of rounds 1-3 everywhere (launch_reduce4 declines), generic kernel for the 1x1 tail
+  WGRAD_CFG_NO_PAIRED_TAILS = 9,   // row-tap kernel without paired row tails
+  WGRAD_CFG_REG = 10,          // (+10) register-staged fast_wgrad_kernel instead of fast_wgrad_dma_kernel
+  WGRAD_CFG_ROWTAP_TARGET = 100,   // (>= 100) the value is the row-tap kernel's block target
+};
+
+// bits of g_fast_ablate / FastGeom::flags above the SRHIP_EPI_* bits (GRADDATA is 0x40)
+constexpr int FAST_EPI_MASK = 0x3f;          // the SRHIP_EPI_* bits an epilogue acts on
+constexpr int FAST_ABL_NO_LOADS = 0x100;     // register-staged kernel: no in-loop loads (timing only, wrong results)
+constexpr int FAST_ABL_NO_BARRIER = 0x200;   // register-staged kernel: no barrier (timing only, wrong results)
+constexpr int FAST_ABL_TIMING = FAST_ABL_NO_LOADS | FAST_ABL_NO_BARRIER;
+constexpr int FAST_ABL_PLAIN_STORES = 0x400; // plain instead of non-temporal epilogue stores (correct results); keeps the one-tile kernels
+
+// byte extent of a [pixels, ld] tensor whose rows hold c floats; false: >= 2 GiB (no 32-bit buffer offsets)
+inline bool bytes_ok(long pixels, int ld, int c, unsigned* out) {
+  const long b = pixels > 0 ? ((pixels - 1) * (long)ld + c) * 4L : 0;
+  if (b >= (1L << 31)) return false;
+  *out = (unsigned)b;
+  return true;
+}
 
 __device__ inline float4 bufload4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
@@ -208,7 +294,5 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
 // conv_patch8.hip: the 8-wave two-group patch kernel for >= 256 destination channels; -1 = not applicable
 int launch_patch8(const float* src, const float* wt, const float* bias, const float* actmask, float* dst, const FastGeom& g,
                   const PatchGeom& pg, int nbm, int eflags, hipStream_t st);
-extern int g_patch8;
-extern int g_patch8_abl;
 
 }  // namespace srhip

@@ -19,7 +19,7 @@ int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* worksp
                         void* stream, float* db = nullptr, float* bias_ws = nullptr, int* bias_done = nullptr,
                         const float* ymask = nullptr, float slope = 0.f);
 
-// ---- fast path (conv_fast.hip): source channels % 16 == 0, <= 32 taps ------------------------- //
+// ---- fast path (conv_fast_fprop.hip / conv_wgrad_fast.hip): source channels % 16 == 0, <= 32 taps ------------------------- //
 // fprop/dgrad eligibility depends only on the conv's static shape, so the packed-weight layout
 // chosen by srhip_pack_weight and the kernel chosen by srhip_conv2d_* always agree.
 bool fast_fwd_ok(int cin, int cout, int kh, int kw);      // source channels = cin
@@ -92,9 +92,6 @@ int flat_wgrad_ok(int n, int h, int w, int cin, int cout);      // bit mask of s
 size_t flat_wgrad_workspace(int nprob, int x_pp, int dy_pp, int n, int h, int w, int cin, int cout);
 int flat_wgrad(int nprob, const void* const* x, const void* const* dy, int x_pp, int dy_pp, float* const* dw, float* const* db, int accumulate,
                void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldf, void* stream);
-extern int g_flat_blocks;
-extern int g_flat_abl;
-extern int g_flat_f32_k8;
 
 // column sums (elementwise.hip), used for the bias gradient on the generic path
 size_t colsum_workspace_bytes(long rows, int c);

@@ -1,4 +1,4 @@
-// Persistent form of the stride-1 3x3 patch kernel (conv_fast.hip: conv_patch_kernel) for gfx950.
+// Persistent form of the stride-1 3x3 patch kernel (conv_fast_fprop.hip: conv_patch_kernel) for gfx950.
 //
 // conv_patch_kernel runs one 128-pixel x BN tile per block: at the bench shape 1536 blocks on 768 slots, i.e. two
 // lock-stepped rounds, each paying its own cold prologue (descriptor / address set-up, the patch and the first weight
@@ -22,8 +22,6 @@
 #include "conv_dev.h"
 
 namespace srhip {
-
-extern int g_fast_ablate;
 
 // ablation helpers: keep a value alive / make it opaque without an instruction (vector-register constraints only exist in the device pass)
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -10,7 +10,7 @@
 //     dW[co][ci][kh][kw] = sum over flat p of dy[p][co] * x[p + (kh-1)*(W+1) + (kw-1)][ci]
 // (a shift that leaves the image lands on a zero pixel), so the K loop of the weight gradient needs no row / column / image
 // bookkeeping at all: a chunk is 16 consecutive flat pixels, its operands are 16 (dy) and 18 (x, three kw taps) consecutive rows
-// of the planes, and the position travels in the buffer instructions' scalar offset.  wgrad_rowtap_kernel (conv_fast.hip) spent
+// of the planes, and the position travels in the buffer instructions' scalar offset.  wgrad_rowtap_kernel (conv_wgrad_fast.hip) spent
 // ~190 scalar and ~160 vector instructions per 18 MFMAs on exactly that bookkeeping and on splitting / transposing fp32
 // fragments (profiles/r04_sq_wait_buckets_roofline_kernels.txt: a wave spent 39 % of its life issuing them).
 //
@@ -872,7 +872,6 @@ __global__ __launch_bounds__(256) void pp_to_f32_kernel(const __bf16* __restrict
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------- //
-extern int g_conv_math;
 int g_flat_abl = 0;         // srhip_debug_set(13, bits): timing-only ablations of wgrad_flat_kernel
 int g_flat_f32_k8 = 1;      // srhip_debug_set(14, v): 0 = one fp32 operand always takes the 4-wave kernel (1: the 8-wave kernel where its tile fits)
 int g_flat_blocks = 768;      // srhip_debug_set(12, n): split-K block target of wgrad_flat_kernel

@@ -935,7 +935,6 @@ __global__ __launch_bounds__(256) void ga_sgam_bwd_dkv_x3_kernel(const float* __
 }
 
 int g_sgam_cfg = 0;   // srhip_debug_set(4, v): 1 = the exact-fp32 SGAM kernels in every arithmetic mode (A/B and tests)
-extern int g_conv_math;
 static inline bool ga_split_math() { return g_conv_math >= 1 && g_sgam_cfg != 1; }
 
 static inline int ga_nsplit(int hw) { return cdiv(hw, GA_PIX); }
