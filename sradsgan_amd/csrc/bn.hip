@@ -2,23 +2,65 @@
 // (reference sradsgan.py:478-479; nn.BatchNorm2d: biased variance for normalisation, unbiased for
 // running_var, momentum 0.1, eps 1e-5).  HBM-bound: forward = 2 reads + 1 write of the tensor,
 // backward = 5 reads + 1 write (dy, x, y twice; x-hat is recomputed, never stored).
-// Statistics are reduced in two deterministic stages (<= 256 row slabs, then per-column); sums are
-// taken about a per-channel shift (the first row) so E[d^2] - E[d]^2 does not cancel.
+// Statistics are reduced in two deterministic stages (<= 1024 row slabs, then per-column); the forward's sums are
+// taken about a per-channel shift (the first row) and carried in fp64, so E[d^2] - E[d]^2 cancels rounded inputs only.
 #include "common.h"
 
 namespace srhip {
 
 __device__ inline float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
-// ---- stage 1 of every per-channel reduction: MODE 0: (sum d, sum d^2), d = x - shift
-//                                              MODE 1: (sum dz, sum dz*xhat), dz = dy * lrelu'(y)
-template <int MODE>
+__device__ inline void d4acc(double (&s)[4], double a, double b, double c, double d) {
+  s[0] += a; s[1] += b; s[2] += c; s[3] += d;
+}
+
+// ---- stage 1 of the forward statistics: per slab (sum d, sum d^2), d = x - shift (fp32, shift = the tensor's first row), accumulated
+// in fp64.  The shift alone does not protect E[d^2] - E[d]^2: the first row is the image corner, the one pixel that zero padding makes
+// systematically atypical, and with d = O(mean) everywhere an fp32 sum of d^2 leaves invstd 1e-3 off.  d * d is exact in fp64 and the
+// sums carry 29 more bits than their terms, so the subtraction in stage 2 cancels rounded inputs only.  Still one read of x, HBM-bound.
+__global__ __launch_bounds__(256) void bn_stats_stage1(const float* __restrict__ x, double* __restrict__ partial, long rows, int c,
+                                                       long rows_per_block) {
+  __shared__ double red0[256][4], red1[256][4];
+  const int tid = threadIdx.x;
+  const int q = c / 4, nrl = 256 / q;
+  const int cq = tid % q, rl = tid / q;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+  const float4 p0 = *reinterpret_cast<const float4*>(x + cq * 4);
+  if (rl < nrl)
+    for (long r = r0 + rl; r < r1; r += nrl) {
+      const float4 v = *reinterpret_cast<const float4*>(x + (size_t)r * c + cq * 4);
+      const double dx = (double)(v.x - p0.x), dy = (double)(v.y - p0.y), dz = (double)(v.z - p0.z), dw = (double)(v.w - p0.w);
+      d4acc(s0, dx, dy, dz, dw);
+      d4acc(s1, dx * dx, dy * dy, dz * dz, dw * dw);
+    }
+  for (int e = 0; e < 4; ++e) {
+    red0[tid][e] = s0[e];
+    red1[tid][e] = s1[e];
+  }
+  __syncthreads();
+  if (tid < q) {
+    for (int k = 1; k < nrl; ++k)
+      for (int e = 0; e < 4; ++e) {
+        s0[e] += red0[k * q + tid][e];
+        s1[e] += red1[k * q + tid][e];
+      }
+    double* o = partial + (size_t)blockIdx.x * 2 * c;
+    for (int e = 0; e < 4; ++e) {
+      o[tid * 4 + e] = s0[e];
+      o[c + tid * 4 + e] = s1[e];
+    }
+  }
+}
+
+// ---- stage 1 of the backward's per-channel reduction: (sum dz, sum dz*xhat), dz = dy * lrelu'(y)
 __global__ __launch_bounds__(256) void bn_reduce_stage1(const float* __restrict__ a, const float* __restrict__ x,
                                                         const float* __restrict__ y, const float* __restrict__ mean,
                                                         const float* __restrict__ invstd, float* __restrict__ partial,
                                                         long rows, int c, long rows_per_block, float slope, int act,
                                                         const float* __restrict__ gamma = nullptr, const float* __restrict__ beta = nullptr) {
-  // beta != nullptr (MODE 1, round 5): the LeakyReLU mask is the sign of the RECOMPUTED pre-activation (x - mean) * invstd * gamma + beta
+  // beta != nullptr (round 5): the LeakyReLU mask is the sign of the RECOMPUTED pre-activation (x - mean) * invstd * gamma + beta
   // -- the forward's own expression, contraction off in both kernels: the same bits, hence the same sign as y's -- instead of a read
   // of y: 2 reads instead of 3 in this pass, 2 + 1 write instead of 3 + 1 in bn_bwd_apply_kernel (both run at the HBM roofline)
   __shared__ float4 red0[256], red1[256];
@@ -28,48 +70,36 @@ __global__ __launch_bounds__(256) void bn_reduce_stage1(const float* __restrict_
   const long r0 = (long)blockIdx.x * rows_per_block;
   const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
   float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-  float4 p0, p1;
-  if (MODE == 0) {
-    p0 = *reinterpret_cast<const float4*>(x + cq * 4);                     // shift = first row
-  } else {
-    p0 = *reinterpret_cast<const float4*>(mean + cq * 4);
-    p1 = *reinterpret_cast<const float4*>(invstd + cq * 4);
-  }
+  const float4 p0 = *reinterpret_cast<const float4*>(mean + cq * 4);
+  const float4 p1 = *reinterpret_cast<const float4*>(invstd + cq * 4);
   float4 pg = make_float4(0.f, 0.f, 0.f, 0.f), pb = pg;
-  if (MODE == 1 && beta != nullptr) {
+  if (beta != nullptr) {
     pg = *reinterpret_cast<const float4*>(gamma + cq * 4);
     pb = *reinterpret_cast<const float4*>(beta + cq * 4);
   }
   if (rl < nrl)
     for (long r = r0 + rl; r < r1; r += nrl) {
       const size_t o = (size_t)r * c + cq * 4;
-      if (MODE == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(x + o);
-        const float4 d = make_float4(v.x - p0.x, v.y - p0.y, v.z - p0.z, v.w - p0.w);
-        s0 = f4add(s0, d);
-        s1 = f4add(s1, make_float4(d.x * d.x, d.y * d.y, d.z * d.z, d.w * d.w));
-      } else {
-        float4 g = *reinterpret_cast<const float4*>(a + o);
-        const float4 v = *reinterpret_cast<const float4*>(x + o);
-        if (act) {
-          float4 yy;
-          if (beta != nullptr) {
-            yy.x = (v.x - p0.x) * p1.x * pg.x + pb.x;
-            yy.y = (v.y - p0.y) * p1.y * pg.y + pb.y;
-            yy.z = (v.z - p0.z) * p1.z * pg.z + pb.z;
-            yy.w = (v.w - p0.w) * p1.w * pg.w + pb.w;
-          } else {
-            yy = *reinterpret_cast<const float4*>(y + o);
-          }
-          g.x = yy.x > 0.f ? g.x : g.x * slope;
-          g.y = yy.y > 0.f ? g.y : g.y * slope;
-          g.z = yy.z > 0.f ? g.z : g.z * slope;
-          g.w = yy.w > 0.f ? g.w : g.w * slope;
+      float4 g = *reinterpret_cast<const float4*>(a + o);
+      const float4 v = *reinterpret_cast<const float4*>(x + o);
+      if (act) {
+        float4 yy;
+        if (beta != nullptr) {
+          yy.x = (v.x - p0.x) * p1.x * pg.x + pb.x;
+          yy.y = (v.y - p0.y) * p1.y * pg.y + pb.y;
+          yy.z = (v.z - p0.z) * p1.z * pg.z + pb.z;
+          yy.w = (v.w - p0.w) * p1.w * pg.w + pb.w;
+        } else {
+          yy = *reinterpret_cast<const float4*>(y + o);
         }
-        s0 = f4add(s0, g);
-        s1 = f4add(s1, make_float4(g.x * ((v.x - p0.x) * p1.x), g.y * ((v.y - p0.y) * p1.y),
-                                   g.z * ((v.z - p0.z) * p1.z), g.w * ((v.w - p0.w) * p1.w)));
+        g.x = yy.x > 0.f ? g.x : g.x * slope;
+        g.y = yy.y > 0.f ? g.y : g.y * slope;
+        g.z = yy.z > 0.f ? g.z : g.z * slope;
+        g.w = yy.w > 0.f ? g.w : g.w * slope;
       }
+      s0 = f4add(s0, g);
+      s1 = f4add(s1, make_float4(g.x * ((v.x - p0.x) * p1.x), g.y * ((v.y - p0.y) * p1.y),
+                                 g.z * ((v.z - p0.z) * p1.z), g.w * ((v.w - p0.w) * p1.w)));
     }
   red0[tid] = s0;
   red1[tid] = s1;
@@ -89,14 +119,14 @@ __global__ __launch_bounds__(256) void bn_reduce_stage1(const float* __restrict_
 // made 64 dependent trips (22 - 54 us per launch for a few KB of work, ~40 launches per step in the discriminator's serial chain).
 constexpr int BN_SUBS = 64;
 
-// stage 2 (forward): per channel mean / invstd, running statistics
-__global__ void bn_stats_stage2(const float* __restrict__ partial, const float* __restrict__ x, float* __restrict__ mean,
+// stage 2 (forward): per channel mean / invstd, running statistics (fp64 until the results are rounded once to fp32)
+__global__ void bn_stats_stage2(const double* __restrict__ partial, const float* __restrict__ x, float* __restrict__ mean,
                                 float* __restrict__ invstd, float* __restrict__ running_mean,
                                 float* __restrict__ running_var, int nblk, int c, long rows, float eps,
                                 float momentum) {
-  __shared__ float r0[16 * BN_SUBS], r1[16 * BN_SUBS];
+  __shared__ double r0[16 * BN_SUBS], r1[16 * BN_SUBS];
   const int col = blockIdx.x * 16 + (threadIdx.x & 15), sub = threadIdx.x >> 4;      // 16 columns x BN_SUBS slab lanes
-  float a = 0.f, b = 0.f;
+  double a = 0.0, b = 0.0;
   if (col < c)
     for (int k = sub; k < nblk; k += BN_SUBS) {
       a += partial[(size_t)k * 2 * c + col];
@@ -107,21 +137,21 @@ __global__ void bn_stats_stage2(const float* __restrict__ partial, const float* 
   __syncthreads();
   if (sub == 0 && col < c) {
     const int t = threadIdx.x;
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;
     for (int k = 0; k < BN_SUBS; ++k) {
       s1 += r0[t + 16 * k];
       s2 += r1[t + 16 * k];
     }
-    const float n = (float)rows;
-    const float md = s1 / n;
-    float var = s2 / n - md * md;
-    var = var > 0.f ? var : 0.f;
-    const float mu = x[col] + md;
+    const double n = (double)rows;
+    const double md = s1 / n;
+    double var = s2 / n - md * md;
+    var = var > 0.0 ? var : 0.0;
+    const float mu = (float)((double)x[col] + md);
     mean[col] = mu;
-    invstd[col] = rsqrtf(var + eps);
+    invstd[col] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
       running_mean[col] = (1.f - momentum) * running_mean[col] + momentum * mu;
-      const float unb = rows > 1 ? var * (n / (n - 1.f)) : var;
+      const float unb = (float)(rows > 1 ? var * (n / (n - 1.0)) : var);
       running_var[col] = (1.f - momentum) * running_var[col] + momentum * unb;
     }
   }
@@ -417,7 +447,8 @@ using namespace srhip;
 
 extern "C" {
 
-size_t srhip_bn_workspace(long rows, int c) { return (size_t)bn_nblk(rows) * 2 * c * sizeof(float); }
+/* the forward's slab partials are fp64, the backward's fp32: one size serves both */
+size_t srhip_bn_workspace(long rows, int c) { return (size_t)bn_nblk(rows) * 2 * c * sizeof(double); }
 
 int srhip_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean,
                        float* running_var, float* y, float* save_mean, float* save_invstd, void* workspace,
@@ -429,9 +460,9 @@ int srhip_bn_train_fwd(const float* x, const float* gamma, const float* beta, fl
   SRHIP_REQUIRE(workspace && workspace_bytes >= srhip_bn_workspace(rows, c), "bn_train_fwd: workspace too small");
   hipStream_t st = as_stream(stream);
   const long nblk = bn_nblk(rows), rpb = (rows + nblk - 1) / nblk;
-  float* part = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(bn_reduce_stage1<0>, dim3((int)nblk), dim3(256), 0, st, nullptr, x, nullptr, nullptr, nullptr, part,
-                     rows, c, rpb, 0.f, 0);
+  SRHIP_REQUIRE(((uintptr_t)workspace & 7) == 0, "bn_train_fwd: workspace must be 8-byte aligned");
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(bn_stats_stage1, dim3((int)nblk), dim3(256), 0, st, x, part, rows, c, rpb);
   hipLaunchKernelGGL(bn_stats_stage2, dim3(cdiv(c, 16)), dim3(16 * BN_SUBS), 0, st, part, x, save_mean, save_invstd, running_mean,
                      running_var, (int)nblk, c, rows, eps, momentum);
   const long n4 = rows * c / 4;
@@ -505,7 +536,7 @@ static int bn_train_bwd_impl(const float* dy, const float* x, const float* y, co
   hipStream_t st = as_stream(stream);
   const long nblk = bn_nblk(rows), rpb = (rows + nblk - 1) / nblk;
   float* part = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(bn_reduce_stage1<1>, dim3((int)nblk), dim3(256), 0, st, dy, x, y, save_mean, save_invstd, part, rows,
+  hipLaunchKernelGGL(bn_reduce_stage1, dim3((int)nblk), dim3(256), 0, st, dy, x, y, save_mean, save_invstd, part, rows,
                      c, rpb, slope, apply_act, gamma, beta);
   hipLaunchKernelGGL(bn_bwd_stage2, dim3(cdiv(c, 16)), dim3(16 * BN_SUBS), 0, st, part, dgamma, dbeta, (int)nblk, c, acc_gamma, acc_beta);
   const long n4 = rows * c / 4;

@@ -371,35 +371,42 @@ __global__ void maxpool2x2_bwd_kernel(const float* __restrict__ dy, const float*
 }
 
 // column sums of a [rows][ld] matrix, first C columns (bias gradient on the generic conv path).
-// stage 1: <= 1024 blocks, each reduces a contiguous slab of rows with 16-byte loads (T = float4)
-// or scalar loads (T = float); stage 2: 4 row-lanes per column over the block partials.
+// stage 1: <= 256 blocks, each reduces a contiguous slab of rows with 16-byte loads (T = float4)
+// or scalar loads (T = float); stage 2: 16 row-lanes per column over the block partials.
+// A block serves at most 256 column groups at a time and walks the rest in further trips (the scalar form of a C > 256 matrix
+// whose row stride or base address rules out 16-byte loads: 2 - 4 trips).
 template <typename T>
 __global__ void colsum_stage1(const float* __restrict__ dy, float* __restrict__ partial, long rows, int c, int ld,
                               long rows_per_block) {
   constexpr int V = sizeof(T) / 4;
   __shared__ T red[256];
   const int tid = threadIdx.x;
-  const int q = c / V;                       // column groups (q <= 256)
-  const int nrl = 256 / q;                   // row lanes
-  const int cq = tid % q, rl = tid / q;
+  const int q = c / V;                       // column groups
+  const int qb = q < 256 ? q : 256;          // ... served per trip
+  const int nrl = 256 / qb;                  // row lanes
+  const int rl = tid / qb;
   const long r0 = (long)blockIdx.x * rows_per_block;
   const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  T s;
-  for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&s)[e] = 0.f;
-  if (rl < nrl)
-    for (long r = r0 + rl; r < r1; r += nrl) {
-      T v = *reinterpret_cast<const T*>(dy + (size_t)r * ld + cq * V);
-      for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&s)[e] += reinterpret_cast<float*>(&v)[e];
+  for (int g0 = 0; g0 < q; g0 += qb) {
+    const int cq = g0 + tid % qb;
+    T s;
+    for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&s)[e] = 0.f;
+    if (rl < nrl && cq < q)
+      for (long r = r0 + rl; r < r1; r += nrl) {
+        T v = *reinterpret_cast<const T*>(dy + (size_t)r * ld + cq * V);
+        for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&s)[e] += reinterpret_cast<float*>(&v)[e];
+      }
+    red[tid] = s;
+    __syncthreads();
+    if (tid < qb && cq < q) {
+      T t = red[tid];
+      for (int k = 1; k < nrl; ++k) {
+        T v = red[k * qb + tid];
+        for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&t)[e] += reinterpret_cast<float*>(&v)[e];
+      }
+      *reinterpret_cast<T*>(partial + (size_t)blockIdx.x * c + cq * V) = t;
     }
-  red[tid] = s;
-  __syncthreads();
-  if (tid < q) {
-    T t = red[tid];
-    for (int k = 1; k < nrl; ++k) {
-      T v = red[k * q + tid];
-      for (int e = 0; e < V; ++e) reinterpret_cast<float*>(&t)[e] += reinterpret_cast<float*>(&v)[e];
-    }
-    *reinterpret_cast<T*>(partial + (size_t)blockIdx.x * c + tid * V) = t;
+    __syncthreads();
   }
 }
 __global__ void colsum_stage2(const float* __restrict__ partial, float* __restrict__ out, int nblk, int c) {
@@ -424,9 +431,11 @@ static long colsum_nblk(long rows) {
 size_t colsum_workspace_bytes(long rows, int c) { return (size_t)colsum_nblk(rows) * c * sizeof(float); }
 
 int colsum_launch(const float* dy, float* db, void* workspace, long rows, int c, int ld, hipStream_t st) {
+  SRHIP_REQUIRE(rows > 0 && c > 0 && ld >= c, "colsum: bad argument");
+  SRHIP_REQUIRE(c % 4 == 0 ? c <= 1024 : c <= 256, "colsum: too many columns (C <= 1024 in multiples of 4, else C <= 256)");
   const long nblk = colsum_nblk(rows);
   const long rpb = (rows + nblk - 1) / nblk;
-  const bool vec = (c % 4 == 0) && (ld % 4 == 0) && ((uintptr_t)dy % 16 == 0) && c <= 1024;
+  const bool vec = (c % 4 == 0) && (ld % 4 == 0) && ((uintptr_t)dy % 16 == 0);
   if (vec)
     hipLaunchKernelGGL(colsum_stage1<float4>, dim3((int)nblk), dim3(256), 0, st, dy, (float*)workspace, rows, c, ld, rpb);
   else

@@ -230,6 +230,13 @@ def nhwc(t):
     return t.contiguous(memory_format=CL)
 
 
+def _dense16(t):
+    """Dense memory (NHWC for a 4-d tensor) at a 16-byte aligned address, as the float4 reductions require: a copy when t is a
+    non-contiguous view or a view whose storage offset breaks the alignment, t itself otherwise."""
+    t = t.contiguous(memory_format=CL) if t.dim() == 4 else t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def empty_nhwc(n, c, h, w, like):
     return torch.empty((n, c, h, w), device=like.device, dtype=torch.float32, memory_format=CL)
 
@@ -2298,8 +2305,7 @@ class _L1Mean(Function):
     @staticmethod
     def forward(ctx, a, b):
         _require_gpu(a, 'l1_mean')
-        a = nhwc(a) if a.dim() == 4 else a.contiguous()
-        b = b.contiguous(memory_format=CL) if (b.dim() == 4) else b.contiguous()
+        a, b = _dense16(a), _dense16(b)
         if a.shape != b.shape:
             raise ValueError('l1_mean: shapes differ: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
         lib = _hip.lib()
@@ -2382,8 +2388,7 @@ class _MseMean(Function):
     @staticmethod
     def forward(ctx, a, b):
         _require_gpu(a, 'mse_mean')
-        a = nhwc(a) if a.dim() == 4 else a.contiguous()
-        b = b.contiguous(memory_format=CL) if (b.dim() == 4) else b.contiguous()
+        a, b = _dense16(a), _dense16(b)
         if a.shape != b.shape:
             raise ValueError('mse_mean: shapes differ: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
         lib = _hip.lib()
@@ -2910,9 +2915,9 @@ class _SmoothL1Mean(Function):
     @staticmethod
     def forward(ctx, a, b, target):
         _require_gpu(a, 'smooth_l1_mean')
-        a = nhwc(a) if a.dim() == 4 else a.contiguous()
+        a = _dense16(a)
         if b is not None:
-            b = b.contiguous(memory_format=CL) if b.dim() == 4 else b.contiguous()
+            b = _dense16(b)
             if a.shape != b.shape:
                 raise ValueError('smooth_l1_mean: shapes differ: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
         lib = _hip.lib()
