@@ -713,6 +713,28 @@ int srhip_resample_pass_u8(const unsigned char* src, unsigned char* dst, const i
                            int ksize, int n, int h, int w, int c, int axis, int out_size, void* stream);
 int srhip_u8_to_float(const unsigned char* src, float* dst, long count, void* stream);
 
+/* ---- whole-scene super-resolution in overlapping tiles (sradsgan_amd/scene.py; additive, ABI stays 14) ---------- *
+ * srhip_scene_tiles_u8: scene = uint8 [h][w][3] on the device, origins_dev = int [n][2] (y, x) on the device, every tile
+ *   th x tw inside the scene (an origin outside it yields a zero tile, never an out-of-bounds read).  dst = float
+ *   [n][th][tw][3], value / 255: tile k holds the bits srhip_u8_to_float gives for scene[y:y+th, x:x+tw].
+ * srhip_scene_blend_u8: feathered blend of float SR tiles into HR rows [row0, row1) of the scene, gather form.
+ *   Tiles form an ny x nx grid; tile (j, i) covers HR rows ay[j] .. ay[j]+th-1 and columns ax[i] .. ax[i]+tw-1 (th, tw in
+ *   HR pixels here) and is read at tiles_dev[(j % depth) * nx + i] + c*sc + qy*sy + qx*sx (element strides, any memory
+ *   format; a null entry is skipped).  ycover_dev [hr_h][2] / xcover_dev [hr_w][2] hold, per HR row / column, the first
+ *   and one-past-last tile row / column covering it; wy_dev [ny][th], wx_dev [nx][tw] are the 1-D feather tables.  Per
+ *   pixel, in fp32 and in row-major tile order (no atomics, so the result is deterministic):
+ *       w = wy * wx;  acc += w * v;  wsum += w;  out = acc / wsum
+ *   (a pixel one tile covers alone has w = 1 and returns the tile's value, -0 as +0).  out_f32 (float [hr_h][hr_w][3],
+ *   may be null) receives out; out_u8 (uint8 [hr_h][hr_w][3], 4-byte aligned, may be null) receives save_img1's
+ *   quantisation (utils/utils.py:169-187) trunc(clamp(255 out, 0, 255)), NaN written as 0.  Whole dwords are stored
+ *   (4 pixels = 12 bytes per thread) with scalar row heads and tails.                                            */
+int srhip_scene_tiles_u8(const unsigned char* scene, int h, int w, const int* origins_dev, int n, int th, int tw, float* dst,
+                         void* stream);
+int srhip_scene_blend_u8(const float* const* tiles_dev, int depth, long sc, long sy, long sx, const int* ycover_dev,
+                         const int* xcover_dev, const int* ay_dev, const int* ax_dev, const float* wy_dev, const float* wx_dev,
+                         int ny, int nx, int th, int tw, int hr_h, int hr_w, int row0, int row1, unsigned char* out_u8,
+                         float* out_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ SIGNATURES = {
     'srhip_resample_coeffs': (_i, [_i, _i, _i, _vp, _vp]),
     'srhip_resample_pass_u8': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'srhip_u8_to_float': (_i, [_vp, _vp, _l, _vp]),
+    'srhip_scene_tiles_u8': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    'srhip_scene_blend_u8': (_i, [_vp, _i, _l, _l, _l] + [_vp] * 6 + [_i] * 8 + [_vp] * 3),
     'srhip_packed_elems': (_sz, [_i] * 5),
     'srhip_pack_entry_bytes': (_i, []),
     'srhip_packed_is_fast': (_i, [_i] * 5),

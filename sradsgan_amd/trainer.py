@@ -363,6 +363,28 @@ class SRADSGAN(object):
             out.append(arr)
         return tuple(out)
 
+    def mfe_test_scene(self, img_fn, modelpath=None, tile=None, overlap=None):
+        """A whole image file, however large, instead of mfe_test_single's centre crop (no counterpart in the reference):
+        the file is super-resolved in overlapping LR tiles of side `tile` (default crop_size // scale_factor, the LR size
+        the generator was trained on) that overlap by `overlap` (default tile // 4), blended with feathered seams on the
+        device (sradsgan_amd.scene) and written as `SR_<model_name>_<name>` into save_dir with save_img1's quantisation.
+        Tiling approximates a whole-scene forward -- attention sees one tile at a time; the feather hides the seams, it
+        does not remove the difference.  Returns the uint8 HWC array [H * scale, W * scale, 3]."""
+        from PIL import Image
+        from . import scene as sscene
+        self.generator = self._new_generator().to(self.device)
+        if modelpath is not None:
+            self.generator.load_state_dict(torch.load(modelpath, map_location='cpu'), strict=False)
+            ckpt._after_load()
+        self.generator.eval()
+        u8 = torch.from_numpy(np.asarray(Image.open(img_fn).convert('RGB'), dtype=np.uint8).copy())
+        tile = self.crop_size // self.scale_factor if tile is None else tile
+        overlap = tile // 4 if overlap is None else overlap
+        arr = sscene.super_resolve_scene(self.generator, u8, self.scale_factor, tile, overlap).cpu().numpy()
+        os.makedirs(self.save_dir, exist_ok=True)
+        Image.fromarray(arr).save(os.path.join(self.save_dir, 'SR_%s_%s' % (self.model_name, os.path.basename(img_fn))))
+        return arr
+
     # ------------------------------------------------------------------ checkpoints ------------- #
     def save_epoch_network(self, save_dir, network, network_label, iter_label):
         return ckpt.save_epoch_network(save_dir, network, network_label, iter_label)
