@@ -584,6 +584,23 @@ int srhip_mean_bwd(const float* gout, float* dx, long count, void* stream);
 int srhip_gp_norm_penalty_fwd(const float* grads, float* out, void* workspace, size_t workspace_bytes, long npix, int c,
                               void* stream);
 int srhip_gp_norm_penalty_bwd(const float* grads, const float* gout, float* dgrads, long npix, int c, void* stream);
+/* ABI 14 (additive) -- gp_penalty: the gradient penalty under every option of sradsgan.py:624-637 (--grad_penalty_Lp_norm,
+ *           --penalty_type), kinds by value.  norm over the C (<= 4) channels of a pixel: L2 sqrt(sum g^2) (gradient 0 where the
+ *           norm is 0), L1 sum |g| (gradient sign(g), sign(0) = 0), Linf max |g| (the whole gradient, times sign(g), at the FIRST
+ *           channel that attains the maximum, as torch.max(dim); an all-zero pixel gets 0).  penalty: LS (norm - 1)^2, factor
+ *           2 (norm - 1); hinge relu(norm - 1), factor 1 where norm - 1 > 0 in fp32, else 0 (0 at exactly 1).  out = mean over
+ *           npix; bwd: dgrads = gout / npix * factor * d norm / d grads.  Same two-stage fixed-tree sum as gp_norm_penalty, no
+ *           atomics; (L2, LS) here is the arithmetic of gp_norm_penalty, which stays the default path.  Unknown kinds and
+ *           C > 4 are refused. */
+#define SRHIP_GP_NORM_L2 0
+#define SRHIP_GP_NORM_L1 1
+#define SRHIP_GP_NORM_LINF 2
+#define SRHIP_GP_PENALTY_LS 0
+#define SRHIP_GP_PENALTY_HINGE 1
+int srhip_gp_penalty_fwd(const float* grads, float* out, void* workspace, size_t workspace_bytes, long npix, int c, int norm_kind,
+                         int penalty_kind, void* stream);
+int srhip_gp_penalty_bwd(const float* grads, const float* gout, float* dgrads, long npix, int c, int norm_kind, int penalty_kind,
+                         void* stream);
 
 /* ---- data-parallel gradient exchange over RCCL / xGMI (the reference is single-GPU, README.md:91).
  * One communicator per process = per GPU.  Rank 0 calls srhip_dp_unique_id and hands the srhip_dp_id_bytes() bytes

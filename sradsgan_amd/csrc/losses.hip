@@ -1,7 +1,7 @@
 // Loss reductions of the training step (SRADSGAN/model/sradsgan.py): nn.L1Loss (:686, used :834, :838), nn.MSELoss (DSSR's
 // loss_Lp_norm='L2', model/dssr.py:266-269), nn.SmoothL1Loss (NDSRGAN, model/ndsrgan.py:325-351), the WGAN
 // critic means of GANLoss (:35-67, used :847, :876-878) and the gradient-penalty reduction (:630-637: per-pixel L2
-// norm over channels, (norm - 1)^2, mean).  Each is one pass over its input (HBM-bound, 16-byte loads where the
+// norm over channels, (norm - 1)^2, mean; :624-637 for the L1 / Linf norms and the hinge penalty).  Each is one pass over its input (HBM-bound, 16-byte loads where the
 // layout allows) into per-block partial sums, and one single-block pass that adds the partials in a fixed order:
 // deterministic, no atomics.  The scalar results stay on the device; backward kernels read the incoming scalar
 // gradient through a device pointer, so nothing synchronises with the host.
@@ -177,6 +177,79 @@ static inline int ls_blocks(long work_items) {
   return (int)(b < 1 ? 1 : (b > LS_MAXB ? LS_MAXB : b));
 }
 
+// ---- the gradient penalty under every option of sradsgan.py:624-637: norm L2 / L1 / Linf over the channels of a pixel, penalty LS
+// (norm - 1)^2 or hinge relu(norm - 1).  One templated pair; the kinds arrive by value and pick the instantiation on the host.
+enum { GP_L2 = 0, GP_L1 = 1, GP_LINF = 2 };
+enum { GP_LS = 0, GP_HINGE = 1 };
+
+template <int NORM>
+__device__ __forceinline__ float gp_pixel_norm(const float* __restrict__ g, long p, int c) {
+  float q = 0.f;
+  for (int j = 0; j < c; ++j) {
+    const float v = g[p * c + j];
+    if (NORM == GP_L2) q += v * v;
+    else if (NORM == GP_L1) q += fabsf(v);
+    else q = fmaxf(q, fabsf(v));
+  }
+  return NORM == GP_L2 ? sqrtf(q) : q;
+}
+
+// partial[block] = sum over pixels of penalty(norm(g_pixel) - 1), pixel = c consecutive floats (c <= 4)
+template <int NORM, int PEN>
+__global__ __launch_bounds__(256) void gp_opt_partial_kernel(const float* __restrict__ g, float* __restrict__ partial, long npix, int c) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const float d = gp_pixel_norm<NORM>(g, p, c) - 1.f;
+    s += PEN == GP_LS ? d * d : (d > 0.f ? d : 0.f);
+  }
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// d penalty / d g = gout / npix * penalty'(norm - 1) * d norm / d g, as autograd has it:
+//   penalty'  LS: 2 (norm - 1); hinge: 1 where norm - 1 > 0 (in fp32), else 0 (relu's backward: 0 at exactly 1)
+//   d norm    L2: g / norm, 0 where norm == 0; L1: sign(g), sign(0) = 0; Linf: sign(g) at the FIRST channel that attains max|g|
+//             (torch.max(dim) returns the first maximal index), 0 at the others -- an all-zero pixel gets sign(0) = 0
+template <int NORM, int PEN>
+__global__ __launch_bounds__(256) void gp_opt_bwd_kernel(const float* __restrict__ g, const float* __restrict__ gout,
+                                                         float* __restrict__ dg, long npix, int c, float inv_npix) {
+  const float gs = gout[0] * inv_npix;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const float nrm = gp_pixel_norm<NORM>(g, p, c);
+    const float d = nrm - 1.f;
+    const float f = (PEN == GP_LS ? 2.f * d : (d > 0.f ? 1.f : 0.f)) * gs;
+    if (NORM == GP_L2) {
+      const float r = nrm > 0.f ? f / nrm : 0.f;
+      for (int j = 0; j < c; ++j) dg[p * c + j] = r * g[p * c + j];
+    } else if (NORM == GP_L1) {
+      for (int j = 0; j < c; ++j) {
+        const float v = g[p * c + j];
+        dg[p * c + j] = v > 0.f ? f : (v < 0.f ? -f : 0.f);
+      }
+    } else {
+      bool taken = false;
+      for (int j = 0; j < c; ++j) {
+        const float v = g[p * c + j];
+        const bool here = !taken && fabsf(v) == nrm;
+        dg[p * c + j] = here ? (v > 0.f ? f : (v < 0.f ? -f : 0.f)) : 0.f;
+        taken = taken || here;
+      }
+    }
+  }
+}
+
+template <int NORM, int PEN>
+static void gp_opt_launch_fwd(const float* g, float* part, int nb, long npix, int c, hipStream_t st) {
+  hipLaunchKernelGGL((gp_opt_partial_kernel<NORM, PEN>), dim3(nb), dim3(256), 0, st, g, part, npix, c);
+}
+
+template <int NORM, int PEN>
+static void gp_opt_launch_bwd(const float* g, const float* gout, float* dg, long npix, int c, hipStream_t st) {
+  hipLaunchKernelGGL((gp_opt_bwd_kernel<NORM, PEN>), dim3(ls_blocks(npix)), dim3(256), 0, st, g, gout, dg, npix, c,
+                     (float)(1.0 / (double)npix));
+}
+
 }  // namespace srhip
 
 using namespace srhip;
@@ -281,6 +354,53 @@ int srhip_gp_norm_penalty_bwd(const float* grads, const float* gout, float* dgra
   hipLaunchKernelGGL(gp_bwd_kernel, dim3(ls_blocks(npix)), dim3(256), 0, as_stream(stream), grads, gout, dgrads, npix, c,
                      (float)(1.0 / (double)npix));
   return check_launch("gp_norm_penalty_bwd");
+}
+
+static int gp_kinds_ok(const char* what, long npix, int c, int norm_kind, int penalty_kind) {
+  if (!(npix > 0 && c >= 1 && c <= 4)) {
+    set_error("%s: needs npix > 0 and 1 <= C <= 4 (image channels), got %ld / %d", what, npix, c);
+    return 0;
+  }
+  if (norm_kind < SRHIP_GP_NORM_L2 || norm_kind > SRHIP_GP_NORM_LINF || penalty_kind < SRHIP_GP_PENALTY_LS ||
+      penalty_kind > SRHIP_GP_PENALTY_HINGE) {
+    set_error("%s: unknown kind: norm_kind %d (0 L2, 1 L1, 2 Linf), penalty_kind %d (0 LS, 1 hinge)", what, norm_kind, penalty_kind);
+    return 0;
+  }
+  return 1;
+}
+
+int srhip_gp_penalty_fwd(const float* grads, float* out, void* workspace, size_t workspace_bytes, long npix, int c, int norm_kind,
+                         int penalty_kind, void* stream) {
+  if (!gp_kinds_ok("gp_penalty_fwd", npix, c, norm_kind, penalty_kind)) return SRHIP_ERR_ARG;
+  if (!ws_ok("gp_penalty_fwd", workspace, workspace_bytes)) return SRHIP_ERR_WORKSPACE;
+  const int nb = ls_blocks(npix);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t st = as_stream(stream);
+  switch (norm_kind * 2 + penalty_kind) {
+    case 0: gp_opt_launch_fwd<GP_L2, GP_LS>(grads, part, nb, npix, c, st); break;
+    case 1: gp_opt_launch_fwd<GP_L2, GP_HINGE>(grads, part, nb, npix, c, st); break;
+    case 2: gp_opt_launch_fwd<GP_L1, GP_LS>(grads, part, nb, npix, c, st); break;
+    case 3: gp_opt_launch_fwd<GP_L1, GP_HINGE>(grads, part, nb, npix, c, st); break;
+    case 4: gp_opt_launch_fwd<GP_LINF, GP_LS>(grads, part, nb, npix, c, st); break;
+    default: gp_opt_launch_fwd<GP_LINF, GP_HINGE>(grads, part, nb, npix, c, st); break;
+  }
+  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, st, part, nb, (float)(1.0 / (double)npix), out);
+  return check_launch("gp_penalty_fwd");
+}
+
+int srhip_gp_penalty_bwd(const float* grads, const float* gout, float* dgrads, long npix, int c, int norm_kind, int penalty_kind,
+                         void* stream) {
+  if (!gp_kinds_ok("gp_penalty_bwd", npix, c, norm_kind, penalty_kind)) return SRHIP_ERR_ARG;
+  hipStream_t st = as_stream(stream);
+  switch (norm_kind * 2 + penalty_kind) {
+    case 0: gp_opt_launch_bwd<GP_L2, GP_LS>(grads, gout, dgrads, npix, c, st); break;
+    case 1: gp_opt_launch_bwd<GP_L2, GP_HINGE>(grads, gout, dgrads, npix, c, st); break;
+    case 2: gp_opt_launch_bwd<GP_L1, GP_LS>(grads, gout, dgrads, npix, c, st); break;
+    case 3: gp_opt_launch_bwd<GP_L1, GP_HINGE>(grads, gout, dgrads, npix, c, st); break;
+    case 4: gp_opt_launch_bwd<GP_LINF, GP_LS>(grads, gout, dgrads, npix, c, st); break;
+    default: gp_opt_launch_bwd<GP_LINF, GP_HINGE>(grads, gout, dgrads, npix, c, st); break;
+  }
+  return check_launch("gp_penalty_bwd");
 }
 
 }  // extern "C"

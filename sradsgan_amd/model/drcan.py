@@ -176,10 +176,15 @@ class DRCAN(_trainer.SRADSGAN):
     """drcan.py:486-1095: SRADSGAN's trainer (same loss terms, WGAN-GP step, clip, plateau control, checkpoint names) with
     RCAN(n_colors=3, n_resgroups=10, n_resblocks=20, reduction=16, scale) and Discriminator(norm_type='batch',
     use_spectralnorm=False, attention=False) (:507-508).  Validation lines of mfeNew_validate carry drcan_* keys.  `n_resgroups` /
-    `n_resblocks` on args override the depth (tests).  Options the step does not implement raise NotImplementedError, as in
-    SRADSGAN."""
+    `n_resblocks` on args override the depth (tests).  The loss options stay at the reference defaults here: no iteration of the
+    reference's DRCAN step is recorded with another set, so anything else raises NotImplementedError."""
 
     eval_label = 'drcan'
+
+    def _check_loss_options(self):
+        if self.penalty_type != 'LS' or self.grad_penalty_Lp_norm != 'L2' or self.loss_Lp_norm != 'L1' or self.relative:
+            raise NotImplementedError('DRCAN runs the reference defaults: LS penalty, L2 gradient norm, L1 content loss, '
+                                      'non-relativistic GAN; SRADSGAN and SRAGAN take the options')
 
     def __init__(self, args, train_loader=None, test_loader=None):
         super().__init__(args, train_loader=train_loader, test_loader=test_loader)

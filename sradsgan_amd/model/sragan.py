@@ -5,13 +5,15 @@ PAM_Module :480-554 -- same constructors for the arguments that path passes, sam
 fused residual-attention node of the SRADSGAN generator (`ops.rab_block`: conv-LeakyReLU-conv, CLAM, SLAM, 1x1, +x)
 with 64 mid channels; BatchNorm (conv2, tied up-sampler stages) and PixelShuffle+LeakyReLU run through the C ABI.
 SRAGAN's Discriminator (:239-277), GANLoss (:42-74), gradient penalty (:372-418) and training iteration (:539-575) are
-identical to SRADSGAN's: use `model.sradsgan.Discriminator / GANLoss` and `train_step.TrainStep` with this generator."""
+identical to SRADSGAN's: use `model.sradsgan.Discriminator / GANLoss` and `train_step.TrainStep` with this generator, or the
+`SRAGAN(args)` trainer below (sragan.py:279-1380), which is SRADSGAN's trainer around it."""
 import math
 
 import torch
 import torch.nn as nn
 
 from .. import ops
+from .. import trainer as _trainer
 from .base_networks import ChannelAttention, SpatialAttention
 from .layers import HipBatchNorm2d, HipConv2d
 from .sradsgan import CGAM as CAM_Module  # noqa: N811  (base_networks.py:513-554, same arithmetic)
@@ -133,3 +135,30 @@ class GeneratorResNet(nn.Module):
         for i in range(0, len(up), 4):
             out = up[i + 2](up[i + 1](up[i](out)))
         return torch.tanh(self.conv3[0](out))
+
+
+def default_args(**overrides):
+    """main_sragan.py:16-62: SRADSGAN's flags with SRAGAN's defaults (model SRAGAN, x4, batch 16, test batch 16, 4 loader threads,
+    8 CPUs)."""
+    d = dict(model_name='SRAGAN', scale_factor=4, batch_size=16, test_batch_size=16, num_threads=4, n_cpu=8)
+    d.update(overrides)
+    return _trainer.default_args(**d)
+
+
+class SRAGAN(_trainer.SRADSGAN):
+    """sragan.py:279-1380: SRADSGAN's trainer (same loss terms and options, WGAN-GP step, clip, plateau control, checkpoint names)
+    with GeneratorResNet(ResidualBlock_Block_WithAttention, 12 residual blocks x 5 basic blocks) and SRADSGAN's discriminator
+    (:465-470).  Validation lines of mfeNew_validate carry sragan_* keys.  `n_residual_blocks` / `n_basic_blocks` on args override
+    the depth (tests)."""
+
+    eval_label = 'sragan'
+
+    def __init__(self, args, train_loader=None, test_loader=None):
+        super().__init__(args, train_loader=train_loader, test_loader=test_loader)
+        self.n_residual_blocks = getattr(args, 'n_residual_blocks', 12)
+        self.n_basic_blocks = getattr(args, 'n_basic_blocks', 5)
+
+    def _new_generator(self):
+        return GeneratorResNet(ResidualBlock_Block_WithAttention, n_residual_blocks=self.n_residual_blocks,
+                               n_basic_blocks=self.n_basic_blocks, rla_mode='CA-SA', bla_mode='CA-SA', ga_mode='CA-SA',
+                               pool_mode='Avg|Max', upscale_factor=self.scale_factor)

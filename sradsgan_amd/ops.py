@@ -2379,9 +2379,46 @@ class _GpPenalty(Function):
         return dg
 
 
-def gp_penalty(grads):
-    """sradsgan.py:630-637: L2 norm over the channel dim (per pixel), LS penalty, mean."""
-    return _GpPenalty.apply(grads)
+GP_NORMS = {'L2': 0, 'L1': 1, 'Linf': 2}         # SRHIP_GP_NORM_* (--grad_penalty_Lp_norm)
+GP_PENALTIES = {'LS': 0, 'hinge': 1}             # SRHIP_GP_PENALTY_* (--penalty_type)
+
+
+class _GpPenaltyKinds(Function):
+    """srhip_gp_penalty_{fwd,bwd}: any (norm, penalty) pair; the kinds travel by value (nothing synchronises with the host)."""
+
+    @staticmethod
+    def forward(ctx, grads, norm_kind, penalty_kind):
+        _require_gpu(grads, 'gp_penalty')
+        g = nhwc(grads)
+        n, c, h, w = g.shape
+        lib = _hip.lib()
+        out = torch.empty((), device=g.device, dtype=torch.float32)
+        ws = _ws(lib.srhip_reduce_workspace(), g)
+        _hip.check(lib.srhip_gp_penalty_fwd(_p(g), _p(out), _p(ws), ws.numel() * 4, n * h * w, c, norm_kind, penalty_kind, _stream()),
+                   'gp_penalty_fwd')
+        ctx.save_for_backward(g)
+        ctx.kinds = (norm_kind, penalty_kind)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (g,) = ctx.saved_tensors
+        n, c, h, w = g.shape
+        dg = torch.empty_like(g, memory_format=CL)
+        _hip.check(_hip.lib().srhip_gp_penalty_bwd(_p(g), _p(gout.contiguous()), _p(dg), n * h * w, c, ctx.kinds[0], ctx.kinds[1],
+                                                   _stream()), 'gp_penalty_bwd')
+        return dg, None, None
+
+
+def gp_penalty(grads, norm='L2', penalty='LS'):
+    """sradsgan.py:624-637: `norm` ('L2' | 'L1' | 'Linf') over the channel dim (per pixel), `penalty` ('LS': (norm - 1)^2 | 'hinge':
+    relu(norm - 1)), mean.  The defaults take srhip_gp_norm_penalty_*, every other pair srhip_gp_penalty_*."""
+    if norm not in GP_NORMS or penalty not in GP_PENALTIES:
+        raise ValueError('gp_penalty: norm must be one of %s and penalty one of %s, got %r / %r'
+                         % (sorted(GP_NORMS), sorted(GP_PENALTIES), norm, penalty))
+    if norm == 'L2' and penalty == 'LS':
+        return _GpPenalty.apply(grads)
+    return _GpPenaltyKinds.apply(grads, GP_NORMS[norm], GP_PENALTIES[penalty])
 
 
 class _MseMean(Function):

@@ -32,7 +32,19 @@ Differences from the reference that do not change results (DESIGN.md "restructur
   * D(gen_hr) feeds both losses (-weight_gan * mean in loss_G :847-852, +mean in loss_D :877): its graph is walked ONCE with
     upstream +1, which yields the fake term's share of D's gradients and g = d mean / d gen_hr; the generator's backward takes
     (-weight_gan) * g at gen_hr (_compute_onewalk; differs from two walks by the rounding of one multiplication per element);
-  * the discriminator's real and penalty terms are backpropagated on the D stream beside the generator's backward, not after it.
+  * the discriminator's real and penalty terms are backpropagated on the D stream beside the generator's backward, not after it;
+  * relative=True (--relativeGan, :840-844, :868-873) runs NO extra discriminator pass.  With the wgan criterion c(x, True) = -mean(x),
+    c(x, False) = mean(x) the relativistic losses are linear: loss_gan = [c(real - mean(fake), False) + c(fake - mean(real), True)] / 2
+    = mean(D(real)) - mean(D(fake)) and loss_D = [c(real - mean(fake), True) + c(fake - mean(real), False)] / 2 = mean(D(fake)) -
+    mean(D(real)).  D(real) is detached in the G phase, so loss_gan's gradient is that of -mean(D(fake)); loss_D IS the plain loss_D:
+    both arenas receive the plain step's gradients bit for bit.  What differs is the logged loss_gan / loss_G, which need
+    mean(D(real)) -- and the G phase's D(real) (:842) equals the D phase's (:869): D's weights do not change in between (Adam(D) runs
+    after both) and its BatchNorms normalise by batch statistics, so the D phase's mean serves -- and one more running-statistics
+    update.  The reference's order is D(gen), D(real), D(real), D(fake), D(interp); here D(gen) updates, D(real) updates and its
+    update is replayed once (ops.replay_bn_update), the stashed D(gen) update is replayed for D(fake), D(interp) updates: the same
+    five updates in the same order;
+  * the penalty options (penalty_type, grad_penalty_Lp_norm) only change the scalar function of the interpolate's gradient
+    (ops.gp_penalty): the one double backward with weight (1 + lambda_gp) is the same sum for any of them.
 """
 import ctypes
 import os
@@ -77,8 +89,16 @@ class TrainStep:
     def __init__(self, generator, discriminator, feature_extractor, lr=2e-4, b1=0.9, b2=0.999,
                  weight_content=1e-2, weight_gan=1e-3, lambda_gp=10.0, clip_value=0.01, use_gp=True,
                  grad_sync=None, use_graph=False, reuse_d_fake=True, overlap_wgrad=True, overlap_d_step=True,
-                 wgrad_stream=None, d_stream=None):
+                 wgrad_stream=None, d_stream=None, penalty_type='LS', grad_penalty_Lp_norm='L2', loss_Lp_norm='L1', relative=False):
+        for name, value, choices in (('penalty_type', penalty_type, ('LS', 'hinge')),                    # main_sradsgan.py:53-56
+                                     ('grad_penalty_Lp_norm', grad_penalty_Lp_norm, ('L2', 'L1', 'Linf')),
+                                     ('loss_Lp_norm', loss_Lp_norm, ('L1', 'L2'))):
+            if value not in choices:
+                raise ValueError('TrainStep: %s must be one of %s, got %r' % (name, choices, value))
         self.G, self.D, self.F = generator, discriminator, feature_extractor
+        self.penalty_type, self.grad_penalty_Lp_norm = penalty_type, grad_penalty_Lp_norm
+        self.loss_Lp_norm, self.relative = loss_Lp_norm, bool(relative)
+        self._crit = ops.l1_mean if loss_Lp_norm == 'L1' else ops.mse_mean        # criterion_content (sradsgan.py:685-688)
         self.weight_content, self.weight_gan = weight_content, weight_gan
         self.lambda_gp, self.clip_value, self.use_gp = lambda_gp, clip_value, use_gp
         self.lr_G = self.lr_D = lr                       # sradsgan.py:724-725 (halved on plateau, :1021-1027)
@@ -133,14 +153,28 @@ class TrainStep:
             p.requires_grad_(flag)
 
     def gradient_penalty(self, real, fake, alpha):
-        """sradsgan.py:595-641 ('L2' norm over channels => per-pixel, 'LS' penalty); returns the
+        """sradsgan.py:595-641 (norm over channels => per-pixel; self.grad_penalty_Lp_norm, self.penalty_type); returns the
         penalty with its double-backward graph attached (the caller backpropagates it)."""
         interp = (alpha * real + (1 - alpha) * fake).requires_grad_(True)
         self._interp = interp                 # the D step's backward does not need d/d(interp) again (backward_scope stop_at)
         d_out = self.D(interp)
         with ops.no_param_grads():
             (grads,) = torch.autograd.grad(d_out, interp, torch.ones_like(d_out), create_graph=True)
-        return ops.gp_penalty(grads)
+        return ops.gp_penalty(grads, self.grad_penalty_Lp_norm, self.penalty_type)
+
+    def _d_real(self, imgs_hr):
+        """D(imgs_hr) of the D phase (:869 / :876).  relative=True: the G phase's D(imgs_hr) (:842) is this very pass -- same weights,
+        batch statistics -- so only its running-statistics update is applied a second time, right behind the first."""
+        if not self.relative:
+            return self.D(imgs_hr)
+        stash = []
+        for bn in self._bns:
+            bn._stat_stash = stash
+        d_real = self.D(imgs_hr)
+        for bn in self._bns:
+            bn._stat_stash = None
+        ops.replay_bn_update(stash)
+        return d_real
 
     def _compute(self, imgs_lr, imgs_hr, alpha):
         if (self.reuse_d_fake and self.use_gp and self.overlap_wgrad and self.overlap_d_step and self._wgrad_stream is not None
@@ -153,10 +187,10 @@ class TrainStep:
         self._set_d_grad(False)
         self.arena_G.zero_grad()
         gen_hr = G(imgs_lr)
-        pixel = ops.l1_mean(gen_hr, imgs_hr)
+        pixel = self._crit(gen_hr, imgs_hr)
         with torch.no_grad():
             real_feat = F(imgs_hr)
-        content = ops.l1_mean(F(gen_hr), real_feat)
+        content = self._crit(F(gen_hr), real_feat)
         loss_gan = -ops.mean(D(gen_hr))
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
         loss_G.backward()
@@ -165,8 +199,11 @@ class TrainStep:
         self._set_d_grad(True)
         self.arena_D.zero_grad()
         fake = gen_hr.detach()
-        terms = [-ops.mean(D(imgs_hr)), ops.mean(D(fake))]
+        terms = [-ops.mean(self._d_real(imgs_hr)), ops.mean(D(fake))]
         loss_D = terms[0] + terms[1]
+        if self.relative:                                         # the logged values only (module docstring)
+            loss_gan = loss_gan.detach() - terms[0].detach()
+            loss_G = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * loss_gan
         if self.use_gp:
             gp = self.gradient_penalty(imgs_hr, fake, alpha)
             terms.append((1.0 + self.lambda_gp) * gp)             # :639 + :884-886 => 1 + lambda
@@ -329,7 +366,7 @@ class TrainStep:
         self._mark('start')
         gen_hr = G(imgs_lr)
         self._mark('G fwd done')
-        pixel = ops.l1_mean(gen_hr, imgs_hr)
+        pixel = self._crit(gen_hr, imgs_hr)
         fake_feat = F(gen_hr)
         gen_in = gen_hr.detach().requires_grad_(True)            # the discriminator's graph hangs off its own leaf
         stash = []
@@ -340,24 +377,28 @@ class TrainStep:
             bn._stat_stash = None
         _join_side(main, side)
         real_feat.record_stream(main)
-        content = ops.l1_mean(fake_feat, real_feat)
+        content = self._crit(fake_feat, real_feat)
         fake_term = ops.mean(d_gen)
         loss_gan = -fake_term.detach()
         loss_G_own = pixel + self.weight_content * content       # the part of loss_G whose graph is G + VGG
         loss_G = loss_G_own.detach() + self.weight_gan * loss_gan
+        own, neg_fake = loss_G_own.detach(), loss_gan
         self._mark('fwd done (VGG, D(gen), losses)')
         # ---- D stream: real pass, interpolate pass, first-order backward of the penalty ----
         dside.wait_stream(main)
         self._mark('D passes begin (D stream)', dside)
         with torch.cuda.stream(dside):
-            real_term = -ops.mean(D(imgs_hr))                    # update #2 (real)
+            real_term = -ops.mean(self._d_real(imgs_hr))         # update #2 (real; relative: applied twice)
             ops.replay_bn_update(stash)                          # update #3 (the fake pass that is not recomputed)
             fake = gen_hr.detach()
             gp = self.gradient_penalty(imgs_hr, fake, alpha)     # update #4
             gp_term = (1.0 + self.lambda_gp) * gp                # :639 + :884-886 => 1 + lambda
             loss_D = real_term.detach() + fake_term.detach() + self.lambda_gp * gp.detach()
+            if self.relative:                                    # the logged values only: mean(D(real)) is this stream's
+                loss_gan = neg_fake - real_term.detach()
+                loss_G = own + self.weight_gan * loss_gan
         self._mark('D passes + GP first order done (D stream)', dside)
-        for t in (gen_hr, gen_in, d_gen, alpha, fake_term):
+        for t in (gen_hr, gen_in, d_gen, alpha, fake_term) + ((own, neg_fake) if self.relative else ()):
             t.record_stream(dside)
         # ---- main: the one walk of D(gen) ----
         torch.autograd.backward(fake_term, inputs=list(d_params) + [gen_in])
@@ -383,7 +424,7 @@ class TrainStep:
         self._exchange_start('D', producers=[dside])
         main.wait_stream(dside)
         _join_side(main, side)
-        for t in (loss_D, gp):
+        for t in (loss_D, gp) + ((loss_G, loss_gan) if self.relative else ()):
             t.record_stream(main)
         out = dict(loss_G=loss_G, loss_D=loss_D, pixel=pixel.detach(), content=content.detach(), loss_gan=loss_gan,
                    gp=gp.detach(), gen_hr=fake)
@@ -420,7 +461,7 @@ class TrainStep:
         self._mark('start')
         gen_hr = G(imgs_lr)
         self._mark('G fwd done')
-        pixel = ops.l1_mean(gen_hr, imgs_hr)
+        pixel = self._crit(gen_hr, imgs_hr)
         fake_feat = F(gen_hr)
         stash = []
         for bn in self._bns:
@@ -437,14 +478,18 @@ class TrainStep:
         else:
             _join_side(torch.cuda.current_stream(), side)
             real_feat.record_stream(torch.cuda.current_stream())   # allocated in the side stream's pool, read here
-        content = ops.l1_mean(fake_feat, real_feat)
+        content = self._crit(fake_feat, real_feat)
         loss_gan = -ops.mean(d_gen)
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
+        logged = dict(loss_G=loss_G.detach(), loss_gan=loss_gan.detach())
 
         def d_forward():
             # ---------------- discriminator forward passes (sradsgan.py:865-884) ----------------
-            terms = [-ops.mean(D(imgs_hr)), ops.mean(d_gen)]      # update #2 (real)
+            terms = [-ops.mean(self._d_real(imgs_hr)), ops.mean(d_gen)]      # update #2 (real; relative: applied twice)
             loss_D = terms[0] + terms[1]
+            if self.relative:                                     # the logged values only (module docstring)
+                logged['loss_gan'] = logged['loss_gan'] - terms[0].detach()
+                logged['loss_G'] = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * logged['loss_gan']
             ops.replay_bn_update(stash)                           # update #3 (the fake pass that is not recomputed)
             fake = gen_hr.detach()
             if self.use_gp:
@@ -468,7 +513,7 @@ class TrainStep:
             with torch.cuda.stream(dside):
                 loss_D, gp, terms, fake = d_forward()
                 self._mark('D passes + GP first order done (D stream)', dside)
-            for t in (gen_hr, d_gen, alpha):
+            for t in (gen_hr, d_gen, alpha) + ((pixel, content, loss_gan) if self.relative else ()):
                 t.record_stream(dside)
             with ops.backward_scope(skip_params=d_params):    # no discriminator wgrads in the G step (:857 -> :865)
                 torch.autograd.backward(loss_G, inputs=g_params, retain_graph=True)
@@ -484,7 +529,7 @@ class TrainStep:
             self._mark('wgrads done (wgrad stream)', side)
             main.wait_stream(dside)
             _join_side(main, side)
-            for t in (loss_D, gp):
+            for t in (loss_D, gp) + ((logged['loss_G'], logged['loss_gan']) if self.relative else ()):
                 t.record_stream(main)
         else:
             with ops.backward_scope(skip_params=d_params):
@@ -494,8 +539,8 @@ class TrainStep:
             with ops.backward_scope(stop_at=(gen_hr,) + ((self._interp,) if self.use_gp else ())):
                 self._backward_terms(terms, d_params)
         self._exchange_start('D')
-        out = dict(loss_G=loss_G.detach(), loss_D=loss_D.detach(), pixel=pixel.detach(),
-                   content=content.detach(), loss_gan=loss_gan.detach(), gp=gp.detach(), gen_hr=fake)
+        out = dict(loss_G=logged['loss_G'], loss_D=loss_D.detach(), pixel=pixel.detach(),
+                   content=content.detach(), loss_gan=logged['loss_gan'], gp=gp.detach(), gen_hr=fake)
         if os.environ.get('SRHIP_STEP_DEBUG') == '1':
             out['d_gen'] = d_gen.detach()
         return out

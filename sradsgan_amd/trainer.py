@@ -71,9 +71,12 @@ class SRADSGAN(object):
             setattr(self, k, getattr(args, k))
         self.relative = args.relativeGan
         self.loss_Lp_norm = args.loss_Lp_norm
-        if self.penalty_type != 'LS' or self.grad_penalty_Lp_norm != 'L2' or self.loss_Lp_norm != 'L1' or self.relative:
-            raise NotImplementedError('the HIP step implements the reference defaults: LS penalty, L2 gradient norm, L1 '
-                                      'content loss, non-relativistic GAN (sradsgan.py:595-641, 829-892)')
+        for name, value, choices in (('penalty_type', self.penalty_type, ('LS', 'hinge')),              # main_sradsgan.py:53-56 `choices`
+                                     ('grad_penalty_Lp_norm', self.grad_penalty_Lp_norm, ('L2', 'L1', 'Linf')),
+                                     ('loss_Lp_norm', self.loss_Lp_norm, ('L1', 'L2'))):
+            if value not in choices:
+                raise ValueError('--%s must be one of %s, got %r' % (name, choices, value))
+        self._check_loss_options()
         if not torch.cuda.is_available():
             raise Exception('No GPU found, please run without --gpu_mode=False')               # main_sradsgan.py:95-96
         # generator depth: the reference hard-codes 12 groups x 3 blocks (:669-671); overridable for tests
@@ -97,6 +100,16 @@ class SRADSGAN(object):
         self.log_dict = OrderedDict()
         self.loss_log_path = os.path.join(self.save_dir, 'loss_log.txt')
         self.val_log_path = os.path.join(self.save_dir, 'val_log.txt')
+
+    # (grad_penalty_Lp_norm, penalty_type) pairs the trainer runs: those with a recorded iteration of the reference to hold the
+    # whole step against (tests/golden/train_small.npz, gan_options.npz).  TrainStep and ops.gp_penalty take all six.
+    penalty_pairs = (('L2', 'LS'), ('L1', 'LS'), ('Linf', 'hinge'))
+
+    def _check_loss_options(self):
+        if (self.grad_penalty_Lp_norm, self.penalty_type) not in self.penalty_pairs:
+            raise NotImplementedError('the trainer runs the penalties with a recorded reference iteration, (norm, penalty) in %s, got '
+                                      '(%r, %r); TrainStep takes any pair (sradsgan.py:595-641)'
+                                      % (self.penalty_pairs, self.grad_penalty_Lp_norm, self.penalty_type))
 
     # ------------------------------------------------------------------ networks ---------------- #
     def _new_generator(self):
@@ -139,7 +152,9 @@ class SRADSGAN(object):
             self._alpha_rng = np.random.RandomState(1234 + self.rank)                           # alpha drawn per rank
         self.step = TrainStep(self.generator, self.discriminator, self.feature_extractor, lr=self.lr, b1=self.b1, b2=self.b2,
                               weight_content=self.weight_content, weight_gan=self.weight_gan, lambda_gp=self.lambda_gp,
-                              clip_value=self.clip_value, use_gp=bool(self.gp), grad_sync=getattr(self, 'grad_sync', None))
+                              clip_value=self.clip_value, use_gp=bool(self.gp), grad_sync=getattr(self, 'grad_sync', None),
+                              penalty_type=self.penalty_type, grad_penalty_Lp_norm=self.grad_penalty_Lp_norm,
+                              loss_Lp_norm=self.loss_Lp_norm, relative=bool(self.relative))
 
     def _batch(self, item, test=False):
         """(lr, hr, bc) device float tensors from a loader item: the reference's 4-tuple, a uint8 HR batch [B,H,W,3],
