@@ -672,6 +672,28 @@ int srhip_bn_train_bwd_bwd_acc_x(const float* ddx, const float* dy, const float*
                                  float* acc_gamma, void* workspace, size_t workspace_bytes, long rows, int c, float slope,
                                  int apply_act, void* stream);
 
+/* ---- per-sample normalisations + LeakyReLU of the patch discriminator (base_networks.py:1759-1767), NHWC x[n][p][c], p = H * W:
+ * `groups` groups of C / groups adjacent channels, one statistic per (sample, group) over m = p * C / groups elements.  Instance norm
+ * (nn.InstanceNorm2d(C)) is groups = C, unbiased = 0, gamma = beta = NULL; the reference's GroupNorm (base_networks.py:12-31) is
+ * groups = 32, unbiased = 1 (x.var(-1)) with per-channel gamma / beta.  gamma and beta are given or NULL together.  Additive to ABI 14.
+ * fwd: y = act((x - mean) * invstd * gamma + beta); saves mean and invstd, [n * groups] each.
+ * bwd: dx (+ addend when not NULL; addend may be dx), dgamma, dbeta; acc_gamma / acc_beta += them when not NULL.  The LeakyReLU mask
+ * is the sign of the pre-activation recomputed from x (no pass reads y).
+ * bwd_bwd: for a cotangent u on dx, the gradients at dy, x and gamma (cotangents on dgamma / dbeta: the host composes that case).
+ * Two-stage reductions without atomics whose order depends on (p, C, groups) only: y, dx, g_dy and g_x of a sample are bit-identical
+ * whatever else is in the batch.  C % 4 == 0, C <= 1024, C % groups == 0, m >= 2, n <= 65535; anything else returns SRHIP_ERR_ARG and
+ * writes nothing.  One workspace size (16-byte aligned) serves the three passes. */
+size_t srhip_gn_workspace(long n, long p, int c);
+int srhip_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* invstd, void* workspace,
+                 size_t workspace_bytes, long n, long p, int c, int groups, int unbiased, float eps, float slope, int apply_act,
+                 void* stream);
+int srhip_gn_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                 const float* addend, float* dx, float* dgamma, float* dbeta, float* acc_gamma, float* acc_beta, void* workspace,
+                 size_t workspace_bytes, long n, long p, int c, int groups, int unbiased, float slope, int apply_act, void* stream);
+int srhip_gn_bwd_bwd(const float* u, const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
+                     const float* invstd, float* g_dy, float* g_x, float* g_gamma, float* acc_gamma, void* workspace,
+                     size_t workspace_bytes, long n, long p, int c, int groups, int unbiased, float slope, int apply_act, void* stream);
+
 /* ---- validation metrics (mfeNew_validate / validate, sradsgan.py:1314-1325; utils/utils.py:923-962):
  *      images quantised like ToPILImage (mul(255).byte(): truncate + wrap, no clamp), NHWC floats in.
  * quant_sse: partial uint64 [n][srhip_metric_blocks()][2] = {sum (a_u8-b_u8)^2, sum b_u8} (exact);

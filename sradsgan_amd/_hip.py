@@ -165,6 +165,10 @@ SIGNATURES = {
     'srhip_bn_train_bwd_acc_xa': (_i, [_vp] * 13 + [_sz, _l, _i, _f, _i, _vp]),
     'srhip_bn_train_bwd_bwd_acc': (_i, [_vp] * 12 + [_sz, _l, _i, _f, _i, _vp]),
     'srhip_bn_train_bwd_bwd_acc_x': (_i, [_vp] * 12 + [_sz, _l, _i, _f, _i, _vp]),
+    'srhip_gn_workspace': (_sz, [_l, _l, _i]),
+    'srhip_gn_fwd': (_i, [_vp] * 7 + [_sz, _l, _l, _i, _i, _i, _f, _f, _i, _vp]),
+    'srhip_gn_bwd': (_i, [_vp] * 13 + [_sz, _l, _l, _i, _i, _i, _f, _i, _vp]),
+    'srhip_gn_bwd_bwd': (_i, [_vp] * 12 + [_sz, _l, _l, _i, _i, _i, _f, _i, _vp]),
     'srhip_metric_blocks': (_i, []),
     'srhip_quant_sse': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'srhip_ssim_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

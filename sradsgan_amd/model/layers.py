@@ -28,6 +28,39 @@ class HipBatchNorm2d(nn.BatchNorm2d):
         return ops.batch_norm_act(x, self, act_slope)
 
 
+class HipInstanceNorm2d(nn.InstanceNorm2d):
+    """nn.InstanceNorm2d(C) as the reference's patch discriminator builds it (base_networks.py:1762-1763: no affine, no running
+    statistics, hence no parameters, no buffers and no state_dict keys) + optional fused LeakyReLU.  Differentiable twice."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=False, track_running_stats=False):
+        if affine or track_running_stats:
+            raise NotImplementedError('HipInstanceNorm2d: nn.InstanceNorm2d(C) without affine and running statistics only')
+        super().__init__(num_features, eps, momentum, False, False)
+
+    def forward(self, x, act_slope=None):
+        if x.shape[1] != self.num_features:
+            raise ValueError('HipInstanceNorm2d: expected %d channels, got %d' % (self.num_features, x.shape[1]))
+        return ops.group_norm_act(x, self.num_features, None, None, self.eps, False, act_slope)
+
+
+class GroupNorm(nn.Module):
+    """The reference's own GroupNorm (base_networks.py:12-31), class name and parameter shapes included: `num_groups` groups of
+    adjacent channels, the UNBIASED variance (x.var(-1)) with eps inside the root, weight = ones and bias = zeros of shape
+    (1, C, 1, 1) + optional fused LeakyReLU.  Differentiable twice."""
+
+    def __init__(self, num_features, num_groups=32, eps=1e-5):
+        super().__init__()
+        if num_features % num_groups:
+            raise ValueError('GroupNorm: %d channels do not divide into %d groups' % (num_features, num_groups))
+        self.weight = nn.Parameter(torch.ones(1, num_features, 1, 1))
+        self.bias = nn.Parameter(torch.zeros(1, num_features, 1, 1))
+        self.num_groups = num_groups
+        self.eps = eps
+
+    def forward(self, x, act_slope=None):
+        return ops.group_norm_act(x, self.num_groups, self.weight, self.bias, self.eps, True, act_slope)
+
+
 class HipDilatedConv2d(nn.Conv2d):
     """nn.Conv2d(k = 3, stride 1, padding = dilation) with dilation 1..3 (AMSSRN's ASPP, amssrn.py:200-209) on the HIP dilated path.
     HipConv2d keeps refusing dilation: its fused epilogues and data-gradient forms are the plain conv's."""

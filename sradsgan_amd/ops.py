@@ -2143,6 +2143,144 @@ def replay_bn_update(stash):
             bn.num_batches_tracked += 1
 
 
+# --------------------------------------------------------------------------------------------- #
+# per-sample normalisations of the patch discriminator (gn.hip): instance norm and the reference's GroupNorm, + LeakyReLU
+# --------------------------------------------------------------------------------------------- #
+
+
+def _gn_reference_bwd(dy, x, gamma, beta, groups, eps, unbiased, slope):
+    """First-order backward of group_norm_act written with differentiable torch ops; only used to differentiate it once more with
+    cotangents the fused second-order pass does not take (like _bn_reference_bwd).  The LeakyReLU mask is a constant."""
+    n, c, h, w = x.shape
+    cpg = c // groups
+    m = cpg * h * w
+    k = m / (m - 1.0) if unbiased else 1.0
+
+    def E(t):
+        return t.reshape(n, groups, -1).mean(-1).repeat_interleave(cpg, 1).view(n, c, 1, 1)
+
+    mean = E(x)
+    invstd = torch.rsqrt(k * E((x - mean) ** 2) + eps)
+    xhat = (x - mean) * invstd
+    ga = gamma.view(1, c, 1, 1) if gamma is not None else 1.0
+    dz = dy
+    if slope is not None:
+        with torch.no_grad():
+            z = xhat * ga + (beta.view(1, c, 1, 1) if beta is not None else 0.0)
+            mask = torch.where(z > 0, 1.0, float(slope))
+        dz = dy * mask
+    a = dz * ga
+    dx = invstd * (a - E(a) - k * xhat * E(a * xhat))
+    if gamma is None:
+        return dx, None, None
+    return dx, (dz * xhat).sum((0, 2, 3)).view_as(gamma), dz.sum((0, 2, 3)).view_as(gamma)
+
+
+def _gn_dims(x, groups):
+    n, c, h, w = x.shape
+    return n, h * w, c, groups
+
+
+def _gn_ws(lib, n, p, c, like):
+    return torch.empty(lib.srhip_gn_workspace(n, p, c) // 4, device=like.device, dtype=torch.float32)
+
+
+def _flat(t):
+    return None if t is None else t.detach().reshape(-1)
+
+
+class _GNBwd(Function):
+    @staticmethod
+    def forward(ctx, dy, x, gamma, beta, mean, invstd, groups, eps, unbiased, slope, acc_gamma=None, acc_beta=None):
+        # acc_gamma / acc_beta: the parameters' gradient slots (direct_param_grads mode), added into by the kernel itself
+        # NB: save the tensors autograd handed us (not layout-converted copies), or the second-order graph through x / dy would be cut
+        dyc, xc = nhwc(dy), nhwc(x)
+        n, p, c, _ = _gn_dims(x, groups)
+        lib = _hip.lib()
+        dx = torch.empty_like(xc, memory_format=CL)
+        dgamma, dbeta = (torch.empty_like(gamma), torch.empty_like(gamma)) if gamma is not None else (None, None)
+        ws = _gn_ws(lib, n, p, c, x)
+        _hip.check(lib.srhip_gn_bwd(_p(dyc), _p(xc), _p(_flat(gamma)), _p(_flat(beta)), _p(mean), _p(invstd), None, _p(dx), _p(dgamma),
+                                    _p(dbeta), _p(acc_gamma), _p(acc_beta), _p(ws), ws.numel() * 4, n, p, c, groups, int(unbiased),
+                                    float(slope or 0.0), int(slope is not None), _stream()), 'gn_bwd')
+        ctx.cfg = (groups, eps, unbiased, slope)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(dy, x, gamma, beta, mean, invstd)
+        return dx, dgamma, dbeta
+
+    @staticmethod
+    def backward(ctx, ddx, ddgamma, ddbeta):
+        dy, x, gamma, beta, mean, invstd = ctx.saved_tensors
+        groups, eps, unbiased, slope = ctx.cfg
+        if ddx is None and ddgamma is None and ddbeta is None:
+            return (None,) * 12
+        if ddx is not None and ddgamma is None and ddbeta is None and not torch.is_grad_enabled():
+            # the gradient-penalty case: one fused second-order pass
+            uc, dyc, xc = nhwc(ddx), nhwc(dy), nhwc(x)
+            n, p, c, _ = _gn_dims(x, groups)
+            lib = _hip.lib()
+            g_dy, g_x = torch.empty_like(xc, memory_format=CL), torch.empty_like(xc, memory_format=CL)
+            g_gamma = torch.empty_like(gamma) if gamma is not None else None
+            ws = _gn_ws(lib, n, p, c, x)
+            slot = None if (gamma is None or _skip_param_grads(gamma)) else _grad_slot(gamma)   # direct_param_grads(): straight into the arena
+            _hip.check(lib.srhip_gn_bwd_bwd(_p(uc), _p(dyc), _p(xc), _p(_flat(gamma)), _p(_flat(beta)), _p(mean), _p(invstd), _p(g_dy), _p(g_x),
+                                            _p(g_gamma), _p(slot), _p(ws), ws.numel() * 4, n, p, c, groups, int(unbiased),
+                                            float(slope or 0.0), int(slope is not None), _stream()), 'gn_bwd_bwd')
+            if slot is not None:
+                g_gamma = None
+            return (g_dy, g_x, g_gamma) + (None,) * 9
+        with torch.enable_grad():
+            dy_, x_ = dy.detach().requires_grad_(True), x.detach().requires_grad_(True)
+            g_ = gamma.detach().requires_grad_(True) if gamma is not None else None
+            outs = _gn_reference_bwd(dy_, x_, g_, beta, groups, eps, unbiased, slope)
+            pairs = [(o, d) for o, d in zip(outs, (ddx, ddgamma, ddbeta)) if d is not None and o is not None]
+            ins = [dy_, x_] + ([g_] if g_ is not None else [])
+            got = torch.autograd.grad([o for o, _ in pairs], ins, [d for _, d in pairs], allow_unused=True)
+        return (got[0], got[1], got[2] if g_ is not None else None) + (None,) * 9
+
+
+class _GNFwd(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps, unbiased, slope):
+        _require_gpu(x, 'group_norm')
+        xc = nhwc(x)
+        n, p, c, _ = _gn_dims(x, groups)
+        lib = _hip.lib()
+        y = torch.empty_like(xc, memory_format=CL)
+        mean = torch.empty(n * groups, device=x.device, dtype=torch.float32)
+        invstd = torch.empty_like(mean)
+        ws = _gn_ws(lib, n, p, c, x)
+        _hip.check(lib.srhip_gn_fwd(_p(xc), _p(_flat(gamma)), _p(_flat(beta)), _p(y), _p(mean), _p(invstd), _p(ws), ws.numel() * 4, n, p, c,
+                                    groups, int(unbiased), float(eps), float(slope or 0.0), int(slope is not None), _stream()), 'gn_fwd')
+        ctx.cfg = (groups, eps, unbiased, slope)
+        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, mean, invstd = ctx.saved_tensors
+        groups, eps, unbiased, slope = ctx.cfg
+        if gamma is not None and not torch.is_grad_enabled() and not _skip_param_grads(gamma, beta):
+            # direct_param_grads(): into the arena slots here, on the stream this node runs on (see _BNTrainFwd.backward)
+            gg, gb = _grad_slot(gamma), _grad_slot(beta)
+            if gg is not None and gb is not None:
+                dx, _, _ = _GNBwd.apply(dy, x, gamma, beta, mean, invstd, groups, eps, unbiased, slope, gg, gb)
+                return dx, None, None, None, None, None, None
+        dx, dgamma, dbeta = _GNBwd.apply(dy, x, gamma, beta, mean, invstd, groups, eps, unbiased, slope)
+        return dx, dgamma, dbeta, None, None, None, None
+
+
+def group_norm_act(x, groups, weight=None, bias=None, eps=1e-5, unbiased=False, slope=None):
+    """Per-sample, per-group normalisation + LeakyReLU on the fused HIP kernels (gn.hip): nn.InstanceNorm2d(C) is groups = C with the
+    biased variance and no affine; the reference's GroupNorm (base_networks.py:12-31) is groups = 32 with the UNBIASED variance and
+    weight / bias of shape (1, C, 1, 1).  x: any memory format; returns channels-last.  Twice differentiable."""
+    if (weight is None) != (bias is None):
+        raise ValueError('group_norm_act: weight and bias are given or left out together')
+    if weight is not None and (weight.numel() != x.shape[1] or not weight.is_contiguous() or not bias.is_contiguous()):
+        raise ValueError('group_norm_act: weight and bias hold one contiguous value per channel')
+    return _GNFwd.apply(x, weight, bias, int(groups), float(eps), bool(unbiased), slope)
+
+
 def max_pool2x2_raw(x):
     _require_gpu(x, 'max_pool2x2')
     x = nhwc(x)

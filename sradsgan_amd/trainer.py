@@ -30,7 +30,8 @@ from . import data as sdata
 from . import dp
 from . import lpips as slpips
 from . import validate as sval
-from .model import Discriminator, FeatureExtractor, GeneratorResNet, ResGroup
+from .model import Discriminator, FeatureExtractor, GeneratorResNet, PatchDiscriminator, ResGroup
+from .model.discriminators import NORM_TYPES
 from .train_step import TrainStep
 
 
@@ -77,6 +78,12 @@ class SRADSGAN(object):
             if value not in choices:
                 raise ValueError('--%s must be one of %s, got %r' % (name, choices, value))
         self._check_loss_options()
+        # the discriminator's normalisation (base_networks.Discriminator's norm_type, the line the reference keeps as a comment at
+        # sradsgan.py:672): absent / None = this trainer's own BatchNorm discriminator, else model.discriminators.PatchDiscriminator
+        self.d_norm_type = getattr(args, 'd_norm_type', None)
+        self.d_attention = bool(getattr(args, 'd_attention', False))
+        if self.d_norm_type is not None and self.d_norm_type not in NORM_TYPES:
+            raise ValueError('args.d_norm_type must be None or one of %r, got %r' % (NORM_TYPES, self.d_norm_type))
         if not torch.cuda.is_available():
             raise Exception('No GPU found, please run without --gpu_mode=False')               # main_sradsgan.py:95-96
         # generator depth: the reference hard-codes 12 groups x 3 blocks (:669-671); overridable for tests
@@ -118,7 +125,9 @@ class SRADSGAN(object):
                                upscale_factor=self.scale_factor)                               # :669-671, :1263-1265
 
     def _new_discriminator(self):
-        return Discriminator()
+        if self.d_norm_type is None:
+            return Discriminator()
+        return PatchDiscriminator(norm_type=self.d_norm_type, attention=self.d_attention)
 
     def _build(self):
         self.generator = self._new_generator()
