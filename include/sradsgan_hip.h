@@ -774,6 +774,30 @@ int srhip_scene_blend_u8(const float* const* tiles_dev, int depth, long sc, long
                          int ny, int nx, int th, int tw, int hr_h, int hr_w, int row0, int row1, unsigned char* out_u8,
                          float* out_f32, void* stream);
 
+/* ---- spectral normalisation of the patch discriminator's conv weights (base_networks.py:73-131; additive, ABI 14) ---- *
+ * All spectral layers of ONE discriminator pass per call.  Per layer, Wb = weight_bar as [cout][k] (k = cin kh kw, OIHW):
+ *     t = Wb^T u, v <- t / (|t| + 1e-12);  s = Wb v, u <- s / (|s| + 1e-12);  sigma = <u, s>;  W = Wb / sigma
+ * u and v are overwritten in place; (u, v, sigma) of the pass are also left in the pass buffer for its backward:
+ *     Gb += G / sigma - (<G, Wb> / sigma^2) u v^T          (G: gradient with respect to W, Gb: weight_bar's gradient slot)
+ * entries_dev: device array of
+ *     struct { const float* wbar; float* u; float* v; long off_sigma, off_weff, off_u, off_v, off_tpart, off_s, off_dpart;
+ *              int cout, k; }                               (srhip_sn_entry_bytes() bytes each)
+ * The table holds the parameters' addresses and OFFSETS for what a pass writes, so one table serves every pass: off_sigma [1],
+ * off_weff [cout k], off_u [cout], off_v [k], off_s [cout] (scratch) and off_tpart (scratch, srhip_sn_tpart_elems(cout, k) floats, an
+ * EVEN offset) count floats from `out`, the pass buffer (8-byte aligned, fresh per pass: it lives until the pass's backward);
+ * off_dpart counts doubles from the backward's `workspace` (srhip_sn_dot_parts(cout, k) doubles per layer).  Regions must not overlap.
+ * grads / gbars: HOST arrays of `count` device addresses (they change per call and travel as kernel arguments): a null grads[i]
+ * skips layer i.  max_cout / max_k: the largest cout and k of the table (they size the grid only).
+ * fp32 operands, sums carried in fp64 and rounded once, whatever the conv arithmetic mode; two-stage reductions in a fixed order,
+ * no atomics; a layer's results depend neither on the other layers of the table nor on the grid.  Any cout >= 1, k >= 1.
+ * Forward: 4 launches, backward: 2 per 32 layers, whatever `count` (<= 65535).                                              */
+int srhip_sn_entry_bytes(void);
+long srhip_sn_tpart_elems(int cout, int k);
+long srhip_sn_dot_parts(int cout, int k);
+int srhip_sn_forward_batched(const void* entries_dev, int count, float* out, int max_cout, int max_k, void* stream);
+int srhip_sn_backward_batched(const void* entries_dev, int count, const float* out, const void* const* grads, void* const* gbars,
+                              void* workspace, int max_cout, int max_k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

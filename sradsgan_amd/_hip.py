@@ -191,6 +191,11 @@ SIGNATURES = {
     'srhip_hat_combine_bwd_workspace': (_sz, [_i] * 3),
     'srhip_hat_combine_bwd': (_i, [_vp] * 14 + [_sz, _f, _i, _l, _i, _i, _vp]),
     'srhip_adam_step': (_i, [_vp] * 5 + [_l] + [_f] * 6 + [_vp]),
+    'srhip_sn_entry_bytes': (_i, []),
+    'srhip_sn_tpart_elems': (_l, [_i, _i]),
+    'srhip_sn_dot_parts': (_l, [_i, _i]),
+    'srhip_sn_forward_batched': (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    'srhip_sn_backward_batched': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 
 _lib = None

@@ -8,9 +8,10 @@ without keys (nn.InstanceNorm2d(C): no affine, no running statistics), 'group' a
 (the reference's own GroupNorm, unbiased variance), 'batch' a BatchNorm2d.  Block 1 never has a norm.  A per-sample norm ('instance',
 'group') or none makes D(x)[i] independent of the other samples of the batch -- what a per-sample gradient penalty assumes.
 
-use_spectralnorm=True is refused: the reference's SpectralNorm advances its power-iteration vectors u and v on EVERY forward, so
+use_spectralnorm=True is refused HERE: the reference's SpectralNorm advances its power-iteration vectors u and v on EVERY forward, so
 D(fake) in the discriminator phase no longer equals D(gen_hr) in the generator phase, and TrainStep (reuse_d_fake, the one-walk
-backward) rests on that equality.  It is its own piece of work."""
+backward) rests on that equality.  The spectral discriminator is its own class, model.spectral.SpectralPatchDiscriminator (same keys as
+the reference's Discriminator(..., use_spectralnorm=True, ...)), which TrainStep runs on its plain order."""
 import torch.nn as nn
 
 from .. import ops

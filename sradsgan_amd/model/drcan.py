@@ -187,9 +187,9 @@ class DRCAN(_trainer.SRADSGAN):
                                       'non-relativistic GAN; SRADSGAN and SRAGAN take the options')
 
     def __init__(self, args, train_loader=None, test_loader=None):
-        if getattr(args, 'd_norm_type', None) is not None or getattr(args, 'd_attention', False):
+        if getattr(args, 'd_norm_type', None) is not None or getattr(args, 'd_attention', False) or getattr(args, 'd_spectralnorm', False):
             raise NotImplementedError("DRCAN trains against Discriminator(norm_type='batch', attention=False) (drcan.py:507-508); "
-                                      'SRADSGAN takes args.d_norm_type / args.d_attention')
+                                      'SRADSGAN takes args.d_norm_type / args.d_attention / args.d_spectralnorm')
         super().__init__(args, train_loader=train_loader, test_loader=test_loader)
         self.n_resgroups = getattr(args, 'n_resgroups', 10)
         self.n_resblocks = getattr(args, 'n_resblocks', 20)

@@ -175,8 +175,8 @@ def _carry_take(token):
 
 def _grad_slot(p):
     """The buffer to accumulate into, or None when direct accumulation is off / impossible for p."""
-    if _state.wgrads is None or p is None or not p.requires_grad:
-        return None
+    if _state.wgrads is None or p is None or not p.requires_grad or not p.is_leaf:     # (a spectral conv's effective weight is no leaf:
+        return None                                                                    # its gradient goes to autograd, ops.spectral_weights projects it)
     g = p.grad
     if g is None or not g.is_contiguous() or g.dtype != torch.float32 or g.device != p.device:
         return None
@@ -347,6 +347,9 @@ def packed_weight(w, mode):
     cout, cin, kh, kw = _wshape(w)
     lib = _hip.lib()
     if not isinstance(w, torch.nn.Parameter):
+        slots = getattr(w, '_srhip_eff_packed', None)
+        if slots is not None:                      # an effective weight of ops.spectral_weights: one image per mode for the tensor's life
+            return _eff_packed(w, slots, mode)
         packed = torch.empty(lib.srhip_packed_elems(cout, cin, kh, kw, mode), device=w.device, dtype=torch.float32)
         _pack_now(w, mode, packed)
         return packed
@@ -376,6 +379,37 @@ def packed_weight(w, mode):
     else:
         _pack_fence(ent)
     return ent[2]
+
+
+eff_pack_stats = {'packed': 0, 'reused': 0}       # effective-weight images packed / found again (tests, tools/time_spectral.py)
+
+
+def _eff_packed(w, slots, mode):
+    """The packed image of an effective weight (a spectral conv's W = weight_bar / sigma of ONE pass: a fresh non-leaf tensor per pass,
+    read by the pass's fprop, its first-order data gradient and the penalty's two second-order passes).  `slots` is a dict the tensor
+    object carries (mode -> [image, pack event, packing stream, streams that waited]): packed on first use, alive exactly as long as
+    the tensor, and -- like _pack_fence for parameters -- a stream other than the packing one waits for the pack's event once."""
+    ent = slots.get(mode)
+    cs = torch.cuda.current_stream()
+    if ent is None:
+        cout, cin, kh, kw = _wshape(w)
+        packed = torch.empty(_hip.lib().srhip_packed_elems(cout, cin, kh, kw, mode), device=w.device, dtype=torch.float32)
+        _pack_now(w, mode, packed)
+        ev = None
+        if not torch.cuda.is_current_stream_capturing():
+            ev = torch.cuda.Event()
+            ev.record()
+        slots[mode] = [packed, ev, cs.cuda_stream, set()]
+        eff_pack_stats['packed'] += 1
+        return packed
+    packed, ev, sid, waited = ent
+    here = cs.cuda_stream
+    if here != sid and here not in waited and ev is not None:
+        cs.wait_event(ev)
+        packed.record_stream(cs)
+        waited.add(here)
+    eff_pack_stats['reused'] += 1
+    return packed
 
 
 def _out_hw(h, w, k, stride, pad):
@@ -1213,6 +1247,143 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act_slope=None, residual=N
     """nn.Conv2d forward with the elementwise tail of its call site fused (bias, LeakyReLU/ReLU,
     residual add).  x: logical NCHW; returns logical NCHW in NHWC memory."""
     return _ConvFwd.apply(x, weight, bias, residual, stride, padding, act_slope)
+
+
+# --------------------------------------------------------------------------------------------- #
+# spectral normalisation of conv weights (csrc/sn.hip; reference base_networks.py:73-131)
+# --------------------------------------------------------------------------------------------- #
+
+
+def _align64(n):
+    return (n + 63) // 64 * 64
+
+
+class SpectralTable:
+    """The spectral layers of one network, [(weight_bar, weight_u, weight_v)], as the device table srhip_sn_forward_batched /
+    srhip_sn_backward_batched walk.  The table holds the parameters' addresses and, for what a pass writes, offsets into a buffer that
+    is allocated per pass: it is built once (again only when a parameter has moved: .to(), dp.ParamArena) and no pass copies anything
+    to the device."""
+
+    def __init__(self, layers):
+        self.layers = [tuple(l) for l in layers]
+        if not self.layers:
+            raise ValueError('SpectralTable: no layers')
+        self.dims = []
+        for wbar, u, v in self.layers:
+            cout, k = wbar.shape[0], wbar[0].numel()
+            if tuple(u.shape) != (cout,) or tuple(v.shape) != (k,):
+                raise ValueError('SpectralTable: weight_u %s / weight_v %s do not fit weight_bar %s' % (tuple(u.shape), tuple(v.shape), tuple(wbar.shape)))
+            self.dims.append((cout, k))
+        self.max_cout, self.max_k = max(d[0] for d in self.dims), max(d[1] for d in self.dims)
+        self._key = self.table = self.last_out = None
+        self.offsets, self.pass_elems, self.ws_doubles = [], 0, 0
+
+    def ensure(self):
+        key = tuple(t.data_ptr() for l in self.layers for t in l)
+        if key == self._key:
+            return
+        import struct
+        lib = _hip.lib()
+        if lib.srhip_sn_entry_bytes() != 88:
+            raise RuntimeError('SpectralTable: the library\'s layer descriptor is %d bytes, this table writes 88' % lib.srhip_sn_entry_bytes())
+        blob, at, dat, self.offsets = bytearray(), 0, 0, []
+        for (wbar, u, v), (cout, k) in zip(self.layers, self.dims):
+            for t in (wbar, u, v):
+                _require_gpu(t, 'spectral_weights')
+                if not t.is_contiguous():
+                    raise ValueError('spectral_weights: parameters must be contiguous')
+            o = {}
+            for name, n in (('sigma', 1), ('u', cout), ('v', k), ('s', cout), ('tpart', lib.srhip_sn_tpart_elems(cout, k)), ('weff', cout * k)):
+                o[name] = at
+                at += _align64(n)
+            # SnEntry (csrc/sn.hip), 88 bytes: Q wbar, Q u, Q v | q off_sigma, off_weff, off_u, off_v, off_tpart, off_s (floats from the pass
+            # buffer), q off_dpart (doubles from the backward's workspace) | i cout, i k
+            blob += struct.pack('<QQQqqqqqqqii', wbar.data_ptr(), u.data_ptr(), v.data_ptr(), o['sigma'], o['weff'], o['u'], o['v'],
+                                o['tpart'], o['s'], dat, cout, k)
+            dat += lib.srhip_sn_dot_parts(cout, k)
+            self.offsets.append(o)
+        self.pass_elems, self.ws_doubles = at, dat
+        self.table = torch.frombuffer(blob, dtype=torch.uint8).to(self.layers[0][0].device)
+        self._key = key
+
+    def forward(self):
+        """One power iteration of every layer on the current stream; returns (pass buffer, [effective weights, views of it])."""
+        self.ensure()
+        wbar0 = self.layers[0][0]
+        out = torch.empty(self.pass_elems, device=wbar0.device, dtype=torch.float32)
+        _hip.check(_hip.lib().srhip_sn_forward_batched(_p(self.table), len(self.layers), _p(out), self.max_cout, self.max_k, _stream()),
+                   'sn_forward_batched')
+        ws = []
+        for (wbar, _, _), o in zip(self.layers, self.offsets):
+            w = out[o['weff']:o['weff'] + wbar.numel()].view(wbar.shape)
+            w._srhip_eff_packed = {}
+            ws.append(w)
+        self.last_out = out
+        return out, ws
+
+    def sigmas(self, out=None):
+        """sigma of every layer as the pass that wrote `out` (default: the last pass) computed it."""
+        out = self.last_out if out is None else out
+        return torch.stack([out[o['sigma']] for o in self.offsets])
+
+    def snapshot(self, out, i):
+        """(u, v, sigma) of layer i as the pass that wrote `out` left them."""
+        o, (cout, k) = self.offsets[i], self.dims[i]
+        return out[o['u']:o['u'] + cout], out[o['v']:o['v'] + k], out[o['sigma']]
+
+    def backward(self, out, grads, slots):
+        """slots[i] += projection of grads[i] (None: layer skipped) with the (u, v, sigma) of the pass that wrote `out`."""
+        self.ensure()
+        n = len(self.layers)
+        tab = ctypes.c_void_p * n
+        gs = [g.contiguous() if g is not None else None for g in grads]
+        for g, s, (wbar, _, _) in zip(gs, slots, self.layers):
+            if g is not None:
+                _require_gpu(g, 'sn_backward')
+                if g.numel() != wbar.numel() or s is None or s.numel() != wbar.numel() or not s.is_contiguous():
+                    raise ValueError('sn_backward: gradient / slot do not fit weight_bar %s' % (tuple(wbar.shape),))
+        ws = torch.empty(max(self.ws_doubles, 1), device=out.device, dtype=torch.float64)
+        _hip.check(_hip.lib().srhip_sn_backward_batched(_p(self.table), n, _p(out), tab(*[g.data_ptr() if g is not None else None for g in gs]),
+                                                       tab(*[s.data_ptr() if (s is not None and g is not None) else None for g, s in zip(gs, slots)]),
+                                                       _p(ws), self.max_cout, self.max_k, _stream()), 'sn_backward_batched')
+
+
+class _SpectralWeights(Function):
+    """(weight_bar, weight_u, weight_v) of every layer of the table -> the effective weights W = weight_bar / sigma of this pass.
+    u and v advance IN PLACE on every call (train, eval, no_grad alike: the reference's SpectralNorm.forward); they are constants of
+    the graph (no gradient), sigma depends on weight_bar.  The backward receives the gradients autograd has summed for each W (the
+    first-order and the penalty's second-order contributions: the projection is linear) and projects them once, with the u, v and
+    sigma THIS pass left in its buffer, straight into weight_bar's arena slot under direct_param_grads()."""
+
+    @staticmethod
+    def forward(ctx, table, *params):
+        ctx.table = table
+        ctx.out, ws = table.forward()
+        ctx.set_materialize_grads(False)
+        return tuple(ws)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        table, n = ctx.table, len(ctx.table.layers)
+        wbars = [l[0] for l in table.layers]
+        gs = [g if ctx.needs_input_grad[1 + i] else None for i, g in enumerate(gs)]
+        ret = [None] * n
+        if any(g is not None for g in gs) and not _skip_param_grads():
+            slots = []
+            for i, (g, wbar) in enumerate(zip(gs, wbars)):
+                slot = _grad_slot(wbar) if g is not None else None
+                if g is not None and slot is None:
+                    slot = ret[i] = torch.zeros_like(wbar)
+                slots.append(slot)
+            table.backward(ctx.out, gs, slots)
+        return (None,) + tuple(ret) + (None,) * (2 * n)
+
+
+def spectral_weights(table):
+    """The effective weights of one pass, in the table's layer order (one batched call; see _SpectralWeights)."""
+    wbars, us, vs = zip(*table.layers)
+    return _SpectralWeights.apply(table, *wbars, *us, *vs)
 
 
 class _SumN(Function):

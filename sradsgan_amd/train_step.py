@@ -43,6 +43,10 @@ Differences from the reference that do not change results (DESIGN.md "restructur
     update.  The reference's order is D(gen), D(real), D(real), D(fake), D(interp); here D(gen) updates, D(real) updates and its
     update is replayed once (ops.replay_bn_update), the stashed D(gen) update is replayed for D(fake), D(interp) updates: the same
     five updates in the same order;
+  * a discriminator with spectral-norm layers (model.spectral) is the exception to the last three points: its weights change with every
+    forward (the power iteration advances u and v), so no pass stands for another.  Such a D always takes the plain order of _compute --
+    D(gen_hr) | [relative: D(real) without a graph, for the logged loss_gan] | D(real), D(fake), D(interp): 4 power iterations per step,
+    5 with relative, in the reference's sequence -- whatever reuse_d_fake says, and is not captured into a graph;
   * the penalty options (penalty_type, grad_penalty_Lp_norm) only change the scalar function of the interpolate's gradient
     (ops.gp_penalty): the one double backward with weight (1 + lambda_gp) is the same sum for any of them.
 """
@@ -53,6 +57,7 @@ import torch
 
 from . import _hip, ops
 from .dp import ParamArena
+from .model.spectral import SpectralNorm, has_spectral_layers
 
 
 def _ptr(t):
@@ -96,6 +101,10 @@ class TrainStep:
             if value not in choices:
                 raise ValueError('TrainStep: %s must be one of %s, got %r' % (name, choices, value))
         self.G, self.D, self.F = generator, discriminator, feature_extractor
+        self._spectral = has_spectral_layers(discriminator)
+        if self._spectral and use_graph:
+            raise ValueError('TrainStep: use_graph=True with a spectral-norm discriminator is not supported (the capture of a step whose '
+                             'power iterations update parameters in place is untested)')
         self.penalty_type, self.grad_penalty_Lp_norm = penalty_type, grad_penalty_Lp_norm
         self.loss_Lp_norm, self.relative = loss_Lp_norm, bool(relative)
         self._crit = ops.l1_mean if loss_Lp_norm == 'L1' else ops.mse_mean        # criterion_content (sradsgan.py:685-688)
@@ -128,6 +137,10 @@ class TrainStep:
         self._calls = 0
         self._static = None
         self._d_params = self.arena_D.params
+        # parameters that never take a gradient (a spectral conv's weight_u / weight_v) stay that way: their arena slots stay zero, so
+        # Adam leaves them alone and only its clip touches them -- as the reference's optimiser and clamp loop do
+        frozen = {id(p) for m in self.D.modules() if isinstance(m, SpectralNorm) for p in m.layer()[1:]}
+        self._d_trainable = [p for p in self.arena_D.params if id(p) not in frozen]
         if dev.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
             ops.plane_pool.release_all()                 # the previous model's padded-plane buffers (other geometries) go back to the allocator
         self._g_parts, self._g_rest = self._plan_g_parts(3)
@@ -149,7 +162,7 @@ class TrainStep:
             self.timeline.append((self._calls, name, ev))
 
     def _set_d_grad(self, flag):
-        for p in self._d_params:
+        for p in self._d_trainable:
             p.requires_grad_(flag)
 
     def gradient_penalty(self, real, fake, alpha):
@@ -165,7 +178,7 @@ class TrainStep:
     def _d_real(self, imgs_hr):
         """D(imgs_hr) of the D phase (:869 / :876).  relative=True: the G phase's D(imgs_hr) (:842) is this very pass -- same weights,
         batch statistics -- so only its running-statistics update is applied a second time, right behind the first."""
-        if not self.relative:
+        if not self.relative or self._spectral:          # (spectral: the G phase ran its own D(imgs_hr), with other weights)
             return self.D(imgs_hr)
         stash = []
         for bn in self._bns:
@@ -177,11 +190,17 @@ class TrainStep:
         return d_real
 
     def _compute(self, imgs_lr, imgs_hr, alpha):
+        if self._spectral:
+            return self._compute_plain(imgs_lr, imgs_hr, alpha)
         if (self.reuse_d_fake and self.use_gp and self.overlap_wgrad and self.overlap_d_step and self._wgrad_stream is not None
                 and self._d_stream is not None):
             return self._compute_onewalk(imgs_lr, imgs_hr, alpha)
         if self.reuse_d_fake:
             return self._compute_shared(imgs_lr, imgs_hr, alpha)
+        return self._compute_plain(imgs_lr, imgs_hr, alpha)
+
+    def _compute_plain(self, imgs_lr, imgs_hr, alpha):
+        """Every pass of the reference, in the reference's sequence (reuse_d_fake=False; always with spectral-norm layers in D)."""
         G, D, F = self.G, self.D, self.F
         # ------------------ generator (sradsgan.py:829-857) ------------------
         self._set_d_grad(False)
@@ -192,6 +211,10 @@ class TrainStep:
             real_feat = F(imgs_hr)
         content = self._crit(F(gen_hr), real_feat)
         loss_gan = -ops.mean(D(gen_hr))
+        g_real = None
+        if self.relative and self._spectral:
+            with torch.no_grad():                                 # :842, detached there: a pass of its own (u and v advance), no graph
+                g_real = ops.mean(D(imgs_hr))
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
         loss_G.backward()
         self._exchange_start('G')
@@ -202,7 +225,7 @@ class TrainStep:
         terms = [-ops.mean(self._d_real(imgs_hr)), ops.mean(D(fake))]
         loss_D = terms[0] + terms[1]
         if self.relative:                                         # the logged values only (module docstring)
-            loss_gan = loss_gan.detach() - terms[0].detach()
+            loss_gan = loss_gan.detach() + (g_real if g_real is not None else -terms[0].detach())
             loss_G = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * loss_gan
         if self.use_gp:
             gp = self.gradient_penalty(imgs_hr, fake, alpha)

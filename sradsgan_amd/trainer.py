@@ -32,6 +32,7 @@ from . import lpips as slpips
 from . import validate as sval
 from .model import Discriminator, FeatureExtractor, GeneratorResNet, PatchDiscriminator, ResGroup
 from .model.discriminators import NORM_TYPES
+from .model.spectral import SpectralPatchDiscriminator, spectral_init_
 from .train_step import TrainStep
 
 
@@ -84,6 +85,15 @@ class SRADSGAN(object):
         self.d_attention = bool(getattr(args, 'd_attention', False))
         if self.d_norm_type is not None and self.d_norm_type not in NORM_TYPES:
             raise ValueError('args.d_norm_type must be None or one of %r, got %r' % (NORM_TYPES, self.d_norm_type))
+        # spectral normalisation of D's block convs (base_networks.Discriminator's use_spectralnorm): model.spectral.SpectralPatchDiscriminator.
+        # The normalisation beside it must be said: the trainer's default D is the BatchNorm one, the reference class's default is '' --
+        # no silent choice between the two
+        self.d_spectralnorm = getattr(args, 'd_spectralnorm', False)
+        if not isinstance(self.d_spectralnorm, bool):
+            raise ValueError('args.d_spectralnorm must be a bool, got %r' % (self.d_spectralnorm,))
+        if self.d_spectralnorm and self.d_norm_type is None:
+            raise ValueError("args.d_spectralnorm needs an explicit args.d_norm_type, one of %r ('' = no normalisation beside the spectral one)"
+                             % (NORM_TYPES,))
         if not torch.cuda.is_available():
             raise Exception('No GPU found, please run without --gpu_mode=False')               # main_sradsgan.py:95-96
         # generator depth: the reference hard-codes 12 groups x 3 blocks (:669-671); overridable for tests
@@ -125,6 +135,8 @@ class SRADSGAN(object):
                                upscale_factor=self.scale_factor)                               # :669-671, :1263-1265
 
     def _new_discriminator(self):
+        if getattr(self, 'd_spectralnorm', False):
+            return SpectralPatchDiscriminator(norm_type=self.d_norm_type, attention=self.d_attention)
         if self.d_norm_type is None:
             return Discriminator()
         return PatchDiscriminator(norm_type=self.d_norm_type, attention=self.d_attention)
@@ -139,7 +151,10 @@ class SRADSGAN(object):
             self.load_epoch_network(model_dir + '/discriminator_param_epoch_%d.pkl' % self.epoch, self.discriminator, strict=True)
         else:
             self.generator.apply(weights_init_normal)                                           # :713-714
-            self.discriminator.apply(weights_init_normal)
+            if getattr(self, 'd_spectralnorm', False):
+                spectral_init_(self.discriminator)              # (the reference's apply() raises for a spectral D: model/spectral.py)
+            else:
+                self.discriminator.apply(weights_init_normal)
             # chain training (:716-721, commented out in the reference and edited by hand per scale): start from the
             # previous scale's checkpoints.  strict=False there still raises on shape mismatches, so the partial load
             # is shape-aware (checkpoint.load_compatible): the up-sampler conv keeps its fresh init across 2^n <-> 3^n
