@@ -798,6 +798,38 @@ int srhip_sn_forward_batched(const void* entries_dev, int count, float* out, int
 int srhip_sn_backward_batched(const void* entries_dev, int count, const float* out, const void* const* grads, void* const* gbars,
                               void* workspace, int max_cout, int max_k, void* stream);
 
+/* ---- scene-classification evaluation of SR outputs (sradsgan_amd/classify.py, Scene_classification_mfe.py; additive, ABI 14) ---- *
+ * srhip_cls_channel_sums: img = uint8 [n][h][w][c] (c <= 4) -> sums = int64 [n][c], the per-image per-channel sums of the raw
+ *   bytes.  Integer arithmetic in two stages (workspace: srhip_cls_channel_sums_workspace bytes, 8-byte aligned): exact.
+ * srhip_cls_preprocess: out[i] = ((float)img[i] - means_dev[i % c]) * (float)(1 / 255.), fp32, one rounding per operation.
+ * The dense layer y[m][n] = x[m][k] w[k][n] + bias[n], 1 <= m <= 64 rows per call, row-major operands, exact fp32 whatever
+ *   srhip_set_conv_math says, no atomics, reproducible bit for bit:
+ *   srhip_cls_dense_fwd: k % 8 == 0, x 16-byte aligned.  Split-K: srhip_cls_dense_chunks(k) slabs of [m][n] partial sums in
+ *     `partials` (a second launch adds them in chunk order), then + bias (may be null), ReLU when relu != 0, dropout when
+ *     dropout != 0: keep(seed, step, e = row * n + col) = first word of Philox4x32-10 with counter {e lo, e hi, step lo, step hi}
+ *     and key {seed lo, seed hi} < 2^31; kept values are doubled, dropped ones are 0.
+ *   srhip_cls_dense_wgrad: dw[k][n] = sum over rows of x[r][k] dy[r][n] in row order; db[n] = sum over rows of dy (db may be null).
+ *   srhip_cls_dense_dgrad: dx[m][k] = dy[m][n] w[k][n]^T in column order, then the backward of the layer that produced the [m][k]
+ *     activation `act`: x2 / 0 by the recomputed dropout mask (dropout != 0), 0 where act <= 0 (relu != 0).
+ * srhip_cls_softmax_ce_fwd_bwd: logits [m][c], c <= 64, labels int32 [m] -> row_loss[r] = -log_softmax(logits[r])[label] in fp32
+ *   (max-subtracted, no clipping; 0 for a label outside [0, c)), loss_sum[0] = their sum in fp64 in a fixed order, and, unless
+ *   dlogits is null, dlogits = (softmax - onehot) * scale.
+ * srhip_cls_confusion: arg[r] = the first index of the row's maximum -> pred[r] (may be null) and ++table[labels[r]][arg[r]]
+ *   (int32 [c][c], may be null; the caller zeroes it, so several calls accumulate; labels outside [0, c) are not counted).     */
+size_t srhip_cls_channel_sums_workspace(int n, int h, int w);
+int srhip_cls_channel_sums(const unsigned char* img, long long* sums, void* workspace, size_t workspace_bytes, int n, int h, int w,
+                           int c, void* stream);
+int srhip_cls_preprocess(const unsigned char* img, const float* means_dev, float* out, long count, int c, void* stream);
+int srhip_cls_dense_chunks(int k);
+int srhip_cls_dense_fwd(const float* x, const float* w, const float* bias, float* y, float* partials, size_t partial_bytes, int m,
+                        int k, int n, int relu, int dropout, unsigned long long seed, unsigned long long step, void* stream);
+int srhip_cls_dense_wgrad(const float* x, const float* dy, float* dw, float* db, int m, int k, int n, void* stream);
+int srhip_cls_dense_dgrad(const float* dy, const float* w, const float* act, float* dx, int m, int k, int n, int relu, int dropout,
+                          unsigned long long seed, unsigned long long step, void* stream);
+int srhip_cls_softmax_ce_fwd_bwd(const float* logits, const int* labels, float* row_loss, double* loss_sum, float* dlogits, int m,
+                                 int c, float scale, void* stream);
+int srhip_cls_confusion(const float* logits, const int* labels, int* pred, int* table, int m, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libsradsgan_hip.so')
 
 _vp, _i, _f, _l, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long, ctypes.c_size_t
+_u64 = ctypes.c_ulonglong
 
 # name -> (restype, argtypes); must list every symbol of include/sradsgan_hip.h (tests check this)
 SIGNATURES = {
@@ -196,6 +197,15 @@ SIGNATURES = {
     'srhip_sn_dot_parts': (_l, [_i, _i]),
     'srhip_sn_forward_batched': (_i, [_vp, _i, _vp, _i, _i, _vp]),
     'srhip_sn_backward_batched': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    'srhip_cls_channel_sums_workspace': (_sz, [_i] * 3),
+    'srhip_cls_channel_sums': (_i, [_vp, _vp, _vp, _sz] + [_i] * 4 + [_vp]),
+    'srhip_cls_preprocess': (_i, [_vp, _vp, _vp, _l, _i, _vp]),
+    'srhip_cls_dense_chunks': (_i, [_i]),
+    'srhip_cls_dense_fwd': (_i, [_vp] * 5 + [_sz] + [_i] * 5 + [_u64, _u64, _vp]),
+    'srhip_cls_dense_wgrad': (_i, [_vp] * 4 + [_i] * 3 + [_vp]),
+    'srhip_cls_dense_dgrad': (_i, [_vp] * 4 + [_i] * 5 + [_u64, _u64, _vp]),
+    'srhip_cls_softmax_ce_fwd_bwd': (_i, [_vp] * 5 + [_i, _i, _f, _vp]),
+    'srhip_cls_confusion': (_i, [_vp] * 4 + [_i, _i, _vp]),
 }
 
 _lib = None

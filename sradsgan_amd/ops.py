@@ -363,8 +363,10 @@ def packed_weight(w, mode):
         new = [weakref.ref(w), mode, packed, w.data_ptr(), w._version, None, 0, set()]
         if w.is_cuda and not torch.cuda.is_current_stream_capturing():
             _pack_event(new)
-        if ent is not None and ent in _registry.entries:
-            _registry.entries.remove(ent)
+        if ent is not None:
+            # by identity: `in` / `remove` compare entries with ==, which compares the weak references' live Parameters element-wise
+            # and raises for every live entry in front of this one
+            _registry.entries = [e for e in _registry.entries if e is not ent]
         slots[mode] = new
         if not getattr(w, '_srhip_static', False):
             _registry.entries.append(new)
