@@ -830,6 +830,35 @@ int srhip_cls_softmax_ce_fwd_bwd(const float* logits, const int* labels, float* 
                                  int c, float scale, void* stream);
 int srhip_cls_confusion(const float* logits, const int* labels, int* pred, int* table, int m, int c, void* stream);
 
+/* ABI 14 (additive) -- forward kernels of the diffusion sampler (csrc/diffusion.hip; model/gdp.py).  Exact fp32 whatever
+ * srhip_set_conv_math says, no atomics (re-runs are bit-identical), NHWC rows with a row stride where noted.
+ *   srhip_diff_gn_fwd: nn.GroupNorm(32, C) (biased variance, per-channel affine) over x [n][p][C] read with row stride ldx, C % 32 == 0,
+ *     C <= 2048; then, if scale / shift (both or neither; [n][C] with row stride ldmod) are given, y = y * (1 + scale) + shift; then SiLU
+ *     if silu != 0.  A sample's statistics read that sample only (two fixed-order stages).  Workspace: srhip_diff_gn_workspace(n, p).
+ *   srhip_diff_silu_fwd: y = x * sigmoid(x) over `count` elements (the time-embedding rows).
+ *   srhip_diff_avgpool2x2_fwd: nn.AvgPool2d(2) on [n][h][w][c] -> [n][h/2][w/2][c], ((a + b) + c + d) * 0.25 in window scan order; odd h
+ *     or w is an argument error.
+ *   srhip_diff_attn_fwd: QKVAttentionLegacy.  qkv [n][t][heads * 3 * ch] with each head's q | k | v as three adjacent runs of ch
+ *     channels; out [n][t][heads * ch] = softmax((q s)(k s)^T) v with s = ch^(-1/4), soft-max in fp32, flash style (no t x t tensor).
+ *     ch is 32 or 64, t is arbitrary, tensors 16-byte aligned.
+ *   srhip_diff_randn: standard normals from Philox4x32-10, key = seed, counter = {element / 4, step}, element = row * ch + channel,
+ *     Box-Muller on the four words; written with row stride ldo.  The bits do not depend on the launch shape.
+ *   srhip_diff_sampler_step: out = c1 * clamp(x0, -1, 1) + c2 * xt + (t_nonzero ? exp(0.5 * logvar) * noise : 0) over rows x ch, every
+ *     tensor with its own row stride; out may be xt.  noise == NULL draws srhip_diff_randn(seed, step)'s values in the kernel.
+ *   srhip_diff_quant_u8: out[rows][ch] = uint8(rint((clamp(x, lo, hi) - lo) / (hi - lo) * 255)), round half to even.                     */
+size_t srhip_diff_gn_workspace(long n, long p);
+int srhip_diff_gn_fwd(const float* x, long ldx, const float* gamma, const float* beta, const float* scale, const float* shift, long ldmod,
+                      float* y, long ldy, void* workspace, size_t workspace_bytes, long n, long p, int c, float eps, int silu,
+                      void* stream);
+int srhip_diff_silu_fwd(const float* x, float* y, long count, void* stream);
+int srhip_diff_avgpool2x2_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
+int srhip_diff_attn_fwd(const float* qkv, float* out, int n, int t, int heads, int ch, void* stream);
+int srhip_diff_randn(float* out, long ldo, long rows, int ch, unsigned long long seed, unsigned long long step, void* stream);
+int srhip_diff_sampler_step(const float* x0, long ldx0, const float* xt, long ldxt, const float* noise, long ldn, float* out, long ldo,
+                            long rows, int ch, float c1, float c2, float logvar, int t_nonzero, unsigned long long seed,
+                            unsigned long long step, void* stream);
+int srhip_diff_quant_u8(const float* x, long ldx, unsigned char* out, long rows, int ch, float lo, float hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

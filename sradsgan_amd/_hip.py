@@ -206,6 +206,14 @@ SIGNATURES = {
     'srhip_cls_dense_dgrad': (_i, [_vp] * 4 + [_i] * 5 + [_u64, _u64, _vp]),
     'srhip_cls_softmax_ce_fwd_bwd': (_i, [_vp] * 5 + [_i, _i, _f, _vp]),
     'srhip_cls_confusion': (_i, [_vp] * 4 + [_i, _i, _vp]),
+    'srhip_diff_gn_workspace': (_sz, [_l, _l]),
+    'srhip_diff_gn_fwd': (_i, [_vp, _l] + [_vp] * 4 + [_l, _vp, _l, _vp, _sz, _l, _l, _i, _f, _i, _vp]),
+    'srhip_diff_silu_fwd': (_i, [_vp, _vp, _l, _vp]),
+    'srhip_diff_avgpool2x2_fwd': (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_diff_attn_fwd': (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_diff_randn': (_i, [_vp, _l, _l, _i, _u64, _u64, _vp]),
+    'srhip_diff_sampler_step': (_i, [_vp, _l] * 4 + [_l, _i, _f, _f, _f, _i, _u64, _u64, _vp]),
+    'srhip_diff_quant_u8': (_i, [_vp, _l, _vp, _l, _i, _f, _f, _vp]),
 }
 
 _lib = None

@@ -23,29 +23,11 @@
 // seed hi}).x < 2^31, e = row * N + column of the layer's output.  Kept values are doubled (inverted scaling at rate 0.5).  The
 // backward recomputes the function; no mask is stored.
 #include "common.h"
+#include "philox.h"
 
 namespace srhip {
 
-// ---- Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85 ----
-__device__ __forceinline__ unsigned philox_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0;
-    c1 = n1;
-    c2 = n2;
-    c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
+// ---- Philox4x32-10 (philox.h): dropout reads the first word ----
 __device__ __forceinline__ bool dropout_keep(unsigned long long seed, unsigned long long step, unsigned long long e) {
   return philox_first((unsigned)e, (unsigned)(e >> 32), (unsigned)step, (unsigned)(step >> 32), (unsigned)seed,
                       (unsigned)(seed >> 32)) < 0x80000000u;
