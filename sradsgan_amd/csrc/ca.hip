@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void ca_mlp_fwd_kernel(const float* __restrict
   if (j < hidden) {
     float d = ca_dot64(fc1 + j * CA_C, sa);
     if (b1) d += b1[j];
-    const float v = fmaxf(d, 0.f);
+    const float v = d < 0.f ? 0.f : d;                  // ReLU that lets a NaN through like ATen's (fmaxf would return 0)
     if ((t & 15) == 0) {
       sh[j] = v;
       hid[b * hidden + j] = v;

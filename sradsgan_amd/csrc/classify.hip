@@ -159,7 +159,7 @@ __global__ void cls_dense_fwd_finish(const float* __restrict__ part, const float
   float v = part[e];
   for (int c = 1; c < chunks; ++c) v += part[(long)c * total + e];
   if (bias) v += bias[(int)(e % n)];
-  if (relu) v = fmaxf(v, 0.f);
+  if (relu) v = v < 0.f ? 0.f : v;                       // lets a NaN through like ATen's ReLU (fmaxf would return 0)
   if (dropout) v = dropout_keep(seed, step, (unsigned long long)e) ? 2.f * v : 0.f;
   y[e] = v;
 }

@@ -236,6 +236,15 @@ __global__ void pixel_shuffle_bwd_kernel(const float* __restrict__ dout, const f
   reinterpret_cast<float4*>(din)[idx] = make_float4(g[0], g[1], g[2], g[3]);
 }
 
+// maximum of one window in scan order with pool_takes (common.h): a NaN in the window surfaces like ATen's max_pool2d (fmaxf drops it)
+__device__ __forceinline__ float pool_max4(float a, float b, float c, float d) {
+  float m = a;
+  if (pool_takes(b, m)) m = b;
+  if (pool_takes(c, m)) m = c;
+  if (pool_takes(d, m)) m = d;
+  return m;
+}
+
 // nn.MaxPool2d(2, 2) on NHWC (vgg19.features[4], [9]); one thread per 4 channels of one output pixel.
 // Ties keep the first element in window scan order (0,0),(0,1),(1,0),(1,1), like ATen.
 __global__ void maxpool2x2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int h, int w, int c) {
@@ -253,10 +262,10 @@ __global__ void maxpool2x2_fwd_kernel(const float* __restrict__ x, float* __rest
   const float4 v00 = *reinterpret_cast<const float4*>(p), v01 = *reinterpret_cast<const float4*>(p + c);
   const float4 v10 = *reinterpret_cast<const float4*>(p + (size_t)w * c), v11 = *reinterpret_cast<const float4*>(p + (size_t)w * c + c);
   float4 o;
-  o.x = fmaxf(fmaxf(v00.x, v01.x), fmaxf(v10.x, v11.x));
-  o.y = fmaxf(fmaxf(v00.y, v01.y), fmaxf(v10.y, v11.y));
-  o.z = fmaxf(fmaxf(v00.z, v01.z), fmaxf(v10.z, v11.z));
-  o.w = fmaxf(fmaxf(v00.w, v01.w), fmaxf(v10.w, v11.w));
+  o.x = pool_max4(v00.x, v01.x, v10.x, v11.x);
+  o.y = pool_max4(v00.y, v01.y, v10.y, v11.y);
+  o.z = pool_max4(v00.z, v01.z, v10.z, v11.z);
+  o.w = pool_max4(v00.w, v01.w, v10.w, v11.w);
   reinterpret_cast<float4*>(y)[idx] = o;
 }
 
@@ -280,10 +289,10 @@ __global__ void maxpool2x2_fwd_idx_kernel(const float* __restrict__ x, float* __
   const float4 v00 = *reinterpret_cast<const float4*>(p), v01 = *reinterpret_cast<const float4*>(p + c);
   const float4 v10 = *reinterpret_cast<const float4*>(p + (size_t)w * c), v11 = *reinterpret_cast<const float4*>(p + (size_t)w * c + c);
   float4 o;
-  o.x = fmaxf(fmaxf(v00.x, v01.x), fmaxf(v10.x, v11.x));
-  o.y = fmaxf(fmaxf(v00.y, v01.y), fmaxf(v10.y, v11.y));
-  o.z = fmaxf(fmaxf(v00.z, v01.z), fmaxf(v10.z, v11.z));
-  o.w = fmaxf(fmaxf(v00.w, v01.w), fmaxf(v10.w, v11.w));
+  o.x = pool_max4(v00.x, v01.x, v10.x, v11.x);
+  o.y = pool_max4(v00.y, v01.y, v10.y, v11.y);
+  o.z = pool_max4(v00.z, v01.z, v10.z, v11.z);
+  o.w = pool_max4(v00.w, v01.w, v10.w, v11.w);
   reinterpret_cast<float4*>(y)[idx] = o;
   auto one = [](float a_, float b_, float c_, float d_) {      // pool_bwd1's comparisons
     int am = 0;

@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256) void hat_ca_fwd_kernel(const float* __restrict
   if (t < hid) {
     float d = b1 ? b1[t] : 0.f;
     for (int k = 0; k < c; ++k) d += w1[t * c + k] * sm[k];
-    const float z = fmaxf(d, 0.f);
+    const float z = d < 0.f ? 0.f : d;                    // ReLU that lets a NaN through like ATen's (fmaxf would return 0)
     sz[t] = z;
     mz[(long)b * (c + hid) + c + t] = z;
   }

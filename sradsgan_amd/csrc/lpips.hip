@@ -19,6 +19,9 @@ constexpr int ST_TH = 8, ST_TW = 16, ST_K = 11, ST_S = 4, ST_P = 2, ST_CO = 64;
 constexpr int ST_PH = (ST_TH - 1) * ST_S + ST_K, ST_PW = (ST_TW - 1) * ST_S + ST_K;     // 39 x 71
 constexpr int ST_ROWK = ST_K * 3;                                                       // 33 (kx, ci) taps per kernel row
 
+// ReLU that lets a NaN through like ATen's (fmaxf would return 0): a NaN image must not score a finite LPIPS
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+
 __global__ __launch_bounds__(256) void lpips_stem_kernel(const float* __restrict__ x, const float* __restrict__ w_hwio,
                                                          const float* __restrict__ bias, float* __restrict__ y, int h, int wd, int ho,
                                                          int wo, int normalize) {
@@ -71,10 +74,10 @@ __global__ __launch_bounds__(256) void lpips_stem_kernel(const float* __restrict
     const int oy = oy0 + r;
     if (oy < ho) {
       float4 o;
-      o.x = fmaxf(acc[r][0] + b.x, 0.f);
-      o.y = fmaxf(acc[r][1] + b.y, 0.f);
-      o.z = fmaxf(acc[r][2] + b.z, 0.f);
-      o.w = fmaxf(acc[r][3] + b.w, 0.f);
+      o.x = relu_nan(acc[r][0] + b.x);
+      o.y = relu_nan(acc[r][1] + b.y);
+      o.z = relu_nan(acc[r][2] + b.z);
+      o.w = relu_nan(acc[r][3] + b.w);
       *reinterpret_cast<float4*>(y + (((size_t)n * ho + oy) * wo + ox) * ST_CO + cg * 4) = o;
     }
   }
