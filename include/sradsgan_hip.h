@@ -73,12 +73,15 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *          1..8 fixed tile shapes of the register-staged kernel
  *   key 1  wgrad: 0 heuristic, 1/2 N tile 64/128, 5 256-wide tiles, 7 no row-tap kernel, 9 row-tap kernel without paired row tails, >= 10 register-staged
  *          kernel, >= 100 split-K block target of the row-tap kernel
- *   key 2  extra dynamic LDS per block (occupancy limiter), key 3 ablation bits (0x100 / 0x200: timing only, wrong results;
+ *   key 3  ablation bits (0x100 / 0x200: timing only, wrong results;
  *          0x400: plain instead of non-temporal epilogue stores, correct results)
  *   key 4  1: the exact-fp32 SGAM kernels in every arithmetic mode (default: split-bf16 products outside SRHIP_MATH_FP32)
  *   key 5  grid of the persistent patch kernel: 0 = three blocks per CU when the conv has more tiles than that (default),
  *          n > 0 = exactly min(n, tiles) blocks whatever the tile count (tests: several tiles per block on small images),
- *          -1 = never (one tile per block: the round-1..3 kernel) */
+ *          -1 = never (one tile per block: the round-1..3 kernel)
+ * The live keys are 0, 1, 3, 4, 5, 7, 10, 11, 12, 14, 17, 18 and 19 (csrc/conv_dev.h names the knob behind each).  Keys 2, 6, 8, 9,
+ * 13, 15 and 16 drove rejected experiments whose code is gone: like any unknown key they return SRHIP_ERR_ARG, and their
+ * numbers are not reused. */
 int srhip_debug_set(int key, int value);
 
 /* ---- in-step kernel timing probe (ABI 6; bench.py: roofline.in_step_avg_launch_ms / in_step_frac) ------------------------------ *

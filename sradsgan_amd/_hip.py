@@ -246,7 +246,8 @@ def lib():
         for item in os.environ.get('SRHIP_DEBUG', '').split(','):      # experiment knobs, "key:value,..." (sradsgan_hip.h)
             if item:
                 key, value = item.split(':')
-                handle.srhip_debug_set(int(key), int(value))
+                if handle.srhip_debug_set(int(key), int(value)) != 0:
+                    raise HipLibraryError('SRHIP_DEBUG: srhip_debug_set refused key %s (%r): unknown or retired key' % (key, item))
         _lib = handle
     return _lib
 

@@ -176,10 +176,10 @@ int srhip_probe_read(float* ms, int* units, int cap) {
 
 /* tuning/experiment knobs; key 0 = fast conv tile configuration (0 = built-in heuristic) */
 int srhip_debug_set(int key, int value) {
-  static int* const knobs[] = {&g_fast_cfg,    &g_wgrad_cfg,  &g_fast_dynlds,  &g_fast_ablate,  &g_sgam_cfg,      &g_pers_grid,  &g_pers_abl,
-                               &g_tail_dbg,    &g_rowtap_addr, &g_rowtap_pipe, &g_patch_ks,     &g_pers_small,    &g_flat_blocks, &g_flat_abl,
-                               &g_flat_f32_k8, &g_patch8,     &g_patch8_abl,   &g_phase_batch,  &g_headconv_rows, &g_pool_epi_any};   // index = key (conv_dev.h)
-  if (key < 0 || key >= (int)(sizeof(knobs) / sizeof(knobs[0]))) return SRHIP_ERR_ARG;
+  static int* const knobs[] = {&g_fast_cfg,    &g_wgrad_cfg, nullptr,        &g_fast_ablate, &g_sgam_cfg,      &g_pers_grid,  nullptr,
+                               &g_tail_dbg,    nullptr,      nullptr,        &g_patch_ks,    &g_pers_small,    &g_flat_blocks, nullptr,
+                               &g_flat_f32_k8, nullptr,      nullptr,        &g_phase_batch, &g_headconv_rows, &g_pool_epi_any};   // index = key (conv_dev.h); nullptr = retired, not reused
+  if (key < 0 || key >= (int)(sizeof(knobs) / sizeof(knobs[0])) || !knobs[key]) return SRHIP_ERR_ARG;
   *knobs[key] = (key == 12 && value <= 0) ? 768 : value;
   return SRHIP_OK;
 }

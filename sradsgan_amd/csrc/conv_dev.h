@@ -1,5 +1,5 @@
 // Shared by the fast convolution translation units (conv_fast_fprop.hip, conv_wgrad_fast.hip,
-// conv_patch_pers.hip, conv_patch8.hip): the debug knobs and the names of their values, geometry structs, the split-bf16
+// conv_patch_pers.hip): the debug knobs and the names of their values, geometry structs, the split-bf16
 // fragment arithmetic, LDS-DMA issue helpers and the patch-tile pixel map.
 #pragma once
 #include "conv_internal.h"
@@ -74,7 +74,8 @@ extern thread_local Dst2Request g_dst2_req;
 
 // ================================================================================================ //
 // Debug / experiment knobs: srhip_debug_set(key, value) (conv_api.hip holds the key table).  Every knob is DEFINED in the
-// file that owns it and declared here, once.
+// file that owns it and declared here, once.  Live keys: 0, 1, 3, 4, 5, 7, 10, 11, 12, 14, 17, 18, 19.  Keys 2, 6, 8, 9, 13, 15
+// and 16 belonged to rejected experiments whose code was removed: they are argument errors now and their numbers are not reused.
 // ================================================================================================ //
 }  // namespace srhip
 extern int g_tail_dbg;        // key 7  (attn_tail.hip): timing-only ablation bits of attn_tail_eval_kernel
@@ -82,20 +83,13 @@ namespace srhip {
 // (the arithmetic mode g_conv_math is not a debug key -- srhip_set_conv_math -- and is read outside the conv files: common.h declares it)
 extern int g_fast_cfg;        // key 0  (conv_fast_fprop.hip): a FastCfg value
 extern int g_wgrad_cfg;       // key 1  (conv_wgrad_fast.hip): a WgradCfg value
-extern int g_fast_dynlds;     // key 2  (conv_fast_fprop.hip): extra dynamic LDS bytes per block = occupancy limiter
 extern int g_fast_ablate;     // key 3  (conv_fast_fprop.hip): FAST_ABL_* bits, OR-ed into FastGeom::flags of forward calls
 extern int g_sgam_cfg;        // key 4  (global_attn.hip)
 extern int g_pers_grid;       // key 5  (conv_patch_pers.hip): > 0 blocks of the persistent patch kernel, -1 never take it
-extern int g_pers_abl;        // key 6  (conv_patch_pers.hip)
-extern int g_rowtap_addr;     // key 8  (conv_wgrad_fast.hip)
-extern int g_rowtap_pipe;     // key 9  (conv_wgrad_fast.hip)
 extern int g_patch_ks;        // key 10 (conv_fast_fprop.hip)
 extern int g_pers_small;      // key 11 (conv_patch_pers.hip)
 extern int g_flat_blocks;     // key 12 (conv_wgrad_flat.hip): values <= 0 mean the default, 768
-extern int g_flat_abl;        // key 13 (conv_wgrad_flat.hip)
 extern int g_flat_f32_k8;     // key 14 (conv_wgrad_flat.hip)
-extern int g_patch8;          // key 15 (conv_patch8.hip)
-extern int g_patch8_abl;      // key 16 (conv_patch8.hip)
 extern int g_phase_batch;     // key 17 (conv_fast_fprop.hip)
 extern int g_headconv_rows;   // key 18 (conv_igemm.hip)
 extern int g_pool_epi_any;    // key 19 (conv_patch_pers.hip)
@@ -290,9 +284,5 @@ extern thread_local PoolRequest g_pool_req;
 int launch_patch_pers(const float* src, const float* wt, const float* bias, const float* residual, const float* actmask,
                       float* dst, const FastGeom& g, const PatchGeom& pg, int nbm, int nbn, bool wide, int prod, int eflags,
                       hipStream_t st);     // g.src_pp / g.dst_pp: src / dst (and, with dst_pp, actmask) point at padded planes
-
-// conv_patch8.hip: the 8-wave two-group patch kernel for >= 256 destination channels; -1 = not applicable
-int launch_patch8(const float* src, const float* wt, const float* bias, const float* actmask, float* dst, const FastGeom& g,
-                  const PatchGeom& pg, int nbm, int eflags, hipStream_t st);
 
 }  // namespace srhip

@@ -1400,7 +1400,6 @@ thread_local Dst2Request g_dst2_req;
 thread_local ResRequest g_res_req;
 thread_local PhaseRequest g_phase_req;
 int g_conv_math = 0;     // SRHIP_MATH_*: 0 exact fp32 MFMA; 1 split-bf16 x3 MFMA; 2 one 16-bit product (fp16 activations / bf16 gradients)
-int g_fast_dynlds = 0;   // experiment knob (srhip_debug_set(2, bytes)): extra dynamic LDS per block = occupancy limiter
 int g_patch_ks = 1;      // srhip_debug_set(10, v): 0 = conv_patch_kernel<64> instead of conv_patch_ks_kernel (bit-identical to the DMA kernel; A/B and pinned tests)
 int g_fast_cfg = 0;      // srhip_debug_set(0, cfg): a FastCfg value (conv_dev.h), 0 = the heuristic of choose_fprop_route
 int g_phase_batch = 1;   // srhip_debug_set(17, v): 1 = the phases of a stride-2 data gradient as one launch of the LDS-DMA kernel
@@ -1489,18 +1488,18 @@ static const float* weight_section(const ConvOperands& a, const FastGeom& g, int
 template <int BM, int BN, int WM, int WN, int BK, int MATH = 0>
 static int launch_reg(const ConvOperands& a, const FastGeom& g, hipStream_t st) {
   const int nbm = cdiv(g.M, BM), nbn = cdiv(g.K, BN);
-  hipLaunchKernelGGL((fast_conv_kernel<BM, BN, WM, WN, BK, MATH>), dim3(nbm * nbn), dim3(WM * WN * 64), g_fast_dynlds, st, a.src,
+  hipLaunchKernelGGL((fast_conv_kernel<BM, BN, WM, WN, BK, MATH>), dim3(nbm * nbn), dim3(WM * WN * 64), 0, st, a.src,
                      weight_section(a, g, MATH), a.bias, a.residual, a.rowscale, a.chanscale, a.actmask, a.dst, g, nbm, nbn);
   return check_launch("fast_conv");
 }
 
 enum class FpropFamily {
   Nothing,    // empty output grid
-  Planes,     // padded-plane operands: conv_patch8 / conv_patch_pers_kernel (their own files); where neither takes the launch, an argument error
+  Planes,     // padded-plane operands: conv_patch_pers_kernel (its own file); where it does not take the launch, an argument error
   Narrow,     // narrow_conv_kernel<nd>
   Dot,        // dot_conv_kernel
   Reg,        // fast_conv_kernel<BM, BN, WM, WN, BK, math>
-  Patch,      // conv_patch8 / conv_patch_pers_kernel where they apply, else conv_patch_kernel<bn, epi, math - 1> or, with ks, conv_patch_ks_kernel<epi>
+  Patch,      // conv_patch_pers_kernel where it applies, else conv_patch_kernel<bn, epi, math - 1> or, with ks, conv_patch_ks_kernel<epi>
   Dma,        // fast_conv_dma_kernel<128, bn, epi, math>
 };
 typedef int (*RegLaunch)(const ConvOperands&, const FastGeom&, hipStream_t);
@@ -1512,7 +1511,7 @@ struct FpropRoute {
   RegLaunch reg = nullptr;   // Reg: launch_reg<BM, BN, WM, WN, BK, math>
   int nd = 0;            // Narrow: destination channels compiled for
   bool ks = false;       // Patch: the K-split one-tile kernel
-  bool try_patch8 = false, try_pers = false;   // Patch / Planes: offer the launch to launch_patch8 / launch_patch_pers first
+  bool try_pers = false;   // Patch / Planes: offer the launch to launch_patch_pers first
   int nbm = 0, nbn = 0;  // Patch / Planes / Dma: tiles along M and N
   bool wide = false;     // Patch / Planes: 128-wide N tiles
   int eflags = 0;        // the SRHIP_EPI_* bits of the call
@@ -1542,7 +1541,6 @@ static FpropRoute choose_fprop_route(const FastGeom& g, const ConvOperands& a) {
       r.nbm = g.N * r.pg.tiles_h * r.pg.tiles_w;
       r.wide = g.K >= 128;
       r.nbn = cdiv(g.K, r.wide ? 128 : 64);
-      r.try_patch8 = r.wide && !a.residual;               // >= 256 destination channels: the 8-wave two-group kernel (conv_patch8.hip)
       r.try_pers = true;
     }
     return r;
@@ -1590,8 +1588,7 @@ static FpropRoute choose_fprop_route(const FastGeom& g, const ConvOperands& a) {
       r.family = FpropFamily::Patch;
       r.math = math16;
       r.try_pers = !(g.flags & FAST_ABL_PLAIN_STORES);    // persistent tile walk (srhip_debug_set(5, -1): never)
-      r.try_patch8 = r.try_pers && r.wide && math16 == 1 && !a.residual;   // >= 256 destination channels: the 8-wave two-group kernel
-      // the one-tile kernels behind them.  SRHIP_MATH_HALF: run-time epilogue flags keep the variant count down
+      // the one-tile kernels behind it.  SRHIP_MATH_HALF: run-time epilogue flags keep the variant count down
       r.ks = math16 == 1 && !r.wide && g_patch_ks && g.C % 32 == 0 && g.C >= 32;   // K-split form of the 64-wide tile
       r.epi = math16 != 1 ? -1 : epi_variant(r.eflags, false);
       if (r.ks && r.epi != 0 && r.epi != SRHIP_EPI_BIAS && r.epi != SRHIP_EPI_RESIDUAL) r.epi = -1;
@@ -1660,7 +1657,7 @@ static int launch_dma(const ConvOperands& a, const FastGeom& g, const FpropRoute
       g_phase_req.launched = 1;
     }
   }
-  hipLaunchKernelGGL((fast_conv_dma_kernel<128, BN, EPI, MATH>), dim3(grid), dim3(256), g_fast_dynlds, st, a.src, weight_section(a, g, MATH),
+  hipLaunchKernelGGL((fast_conv_dma_kernel<128, BN, EPI, MATH>), dim3(grid), dim3(256), 0, st, a.src, weight_section(a, g, MATH),
                      a.bias, a.residual, a.rowscale, a.chanscale, a.actmask, a.dst, g, r.nbm, r.nbn, ps);
   return check_launch("fast_conv_dma");
 }
@@ -1685,10 +1682,6 @@ static int launch_fprop(const ConvOperands& a, const FastGeom& g, const FpropRou
       return SRHIP_OK;
     case FpropFamily::Planes:
     case FpropFamily::Patch: {
-      if (r.try_patch8) {
-        const int rc8 = launch_patch8(a.src, a.wt, a.bias, a.actmask, a.dst, g, r.pg, r.nbm, r.eflags, st);
-        if (rc8 >= 0) return rc8;
-      }
       if (r.try_pers) {
         const int rc = launch_patch_pers(a.src, a.wt, a.bias, a.residual, a.actmask, a.dst, g, r.pg, r.nbm, r.nbn, r.wide, r.math - 1, r.eflags, st);
         if (rc >= 0) return rc;

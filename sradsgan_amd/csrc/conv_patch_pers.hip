@@ -12,7 +12,7 @@
 //     allow NS more operations (vmcnt completes in order on gfx9-class memory pipelines);
 //   * the accumulators are staged through LDS in four 16-row passes inside the patch buffer / ring slot that the last tap
 //     has just released (the next tile's prefetch occupies the others), so the block still needs 50.5 KB: 3 blocks per CU.
-//     (Tried and kept as ablation 64: MFMA operand roles swapped -- weights = rows, pixels = columns -- so that a lane holds 4
+//     (Tried in round 4 and removed: MFMA operand roles swapped -- weights = rows, pixels = columns -- so that a lane holds 4
 //     consecutive channels of one pixel and stores them itself, no LDS transpose, a third of the address arithmetic.  Same
 //     time in split-bf16 and TWICE the HBM write traffic: a wave instruction then writes 32 B per pixel and the memory side
 //     counts 212 MB for 95.6 MB of output (profiles/r04_roofline_pmc_direct_epilogue.txt); the store-bound `half` kernel ran
@@ -23,17 +23,6 @@
 
 namespace srhip {
 
-// ablation helpers: keep a value alive / make it opaque without an instruction (vector-register constraints only exist in the device pass)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define KEEP_IN(x) asm volatile("" ::"v"(x))
-#define KEEP_OUT(x) asm volatile("" : "=v"(x))
-#else
-#define KEEP_IN(x) (void)(x)
-#define KEEP_OUT(x) (void)(x)
-#endif
-
-// ABL: timing-only ablations (wrong results), srhip_debug_set(6, bits) on the <128, bias+lrelu> fprop: 1 stores dropped (out-of-range
-// offsets: issued, never written), 2 no in-place conversion, 4 no MFMAs, 8 no fragment reads, 16 no B DMA in the loop, 32 no epilogue
 // POOL (round 4, BN = 64 with K <= 64 only): the epilogue also reduces the tile's final outputs per channel -- sum, NaN-propagating
 // maximum, first arg-max pixel -- and writes one partial per (image, tile, wave row): the CLAM pooling partials of the RAB tail
 // (clam_pool_partial_kernel's job: a 24 MB read and a launch per RAB) as three more counted stores of the producing conv.
@@ -48,18 +37,16 @@ namespace srhip {
 // forward WRITES them (one more counted store per tile; `actmask` is the word buffer), 2 = the masked data gradient READS them (one
 // 8-byte load per lane and tile instead of eight 16-byte loads of the producer's hi plane: 3 MB instead of 48 at the bench shape).
 // Producer and consumer must walk the same tiles: same image size, same channel count, both BN = 128 (srhip_conv2d_pp_sign_bytes).
-template <int BN, int EPI, int PROD = 0, int ABL = 0, int POOL = 0, int SRCPP = 0, int DSTPP = 0, int SIGNS = 0>
+template <int BN, int EPI, int PROD = 0, int POOL = 0, int SRCPP = 0, int DSTPP = 0, int SIGNS = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv_patch_pers_kernel(
     const float* __restrict__ src, const float* __restrict__ wt, const float* __restrict__ bias,
     const float* __restrict__ residual, const float* __restrict__ actmask, float* __restrict__ dst, FastGeom g,
     PatchGeom pg, int nblk_m, int nblk_n, unsigned dst_bytes, int ndst16, float* __restrict__ pool_out, unsigned pool_sec) {
-  static_assert(POOL == 0 || (BN == 64 && PROD == 0 && ABL == 0), "pooling epilogue: 64-wide tile, split-bf16");
-  static_assert((SRCPP == 0 && DSTPP == 0) || (PROD == 0 && ABL == 0), "padded planes: split-bf16 only");
+  static_assert(POOL == 0 || (BN == 64 && PROD == 0), "pooling epilogue: 64-wide tile, split-bf16");
+  static_assert((SRCPP == 0 && DSTPP == 0) || PROD == 0, "padded planes: split-bf16 only");
   static_assert(DSTPP == 0 || POOL == 0, "a pp destination has no pooling epilogue");
   static_assert(SIGNS == 0 || (BN == 128 && DSTPP == 1 && EPI == (SIGNS == 1 ? 3 : 32)), "sign words: 128-wide tile onto planes, bias + LeakyReLU forward / masked data gradient");
   constexpr bool TILED = PROD == 0;                 // B tiles from the tiled section of the packed weight (conv_internal.h)
-  constexpr int XB = (ABL & 128) ? 2 : 1, XA = (ABL & 256) ? 2 : 1;   // ablations 128 / 256: every B / A DMA issued twice (marginal cost of the streams)
-  constexpr bool DIRECT = (ABL & 64) != 0;          // ablation 64: epilogue straight from the accumulators with the MFMA operand roles swapped (see the header)
   constexpr int NW = 4, BK = 16;
   constexpr int WTM = 64, WTN = BN / 2;
   constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -251,34 +238,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     constexpr int TAP = decltype(tapc)::value;
     constexpr bool FIRST = decltype(firstc)::value != 0;
     constexpr int pbuf = decltype(parc)::value;
-    constexpr int NEWER = XB * BPW + ((TAP >= 1 && TAP <= MAXP) ? XA : 0) + ((FIRST && TAP < 2) ? NS : 0);
+    constexpr int NEWER = BPW + ((TAP >= 1 && TAP <= MAXP) ? 1 : 0) + ((FIRST && TAP < 2) ? NS : 0);
     wait_vmcnt<NEWER>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (TAP < MAXP) issue_a(pbuf ^ 1, TAP, a_coff);
-    if (XA == 2 && TAP < MAXP) issue_a(pbuf ^ 1, TAP, a_coff);
-    if (XB == 2) {
-      if (TAP + 2 < 9) issue_b((TAP + 2) % 3, TAP + 2, cc);
-      else issue_b((TAP + 2) % 3, TAP + 2 - 9, b_ncc);
-    }
-    if (ABL & 16) {
-#pragma unroll
-      for (int j = 0; j < BPW; ++j) lds_dma16_buf(F_OOB, rs_b, b_dst + ((TAP + 2) % 3) * BSTAGE_B + j * 1024);
-    } else if (TAP + 2 < 9) issue_b((TAP + 2) % 3, TAP + 2, cc);
+    if (TAP + 2 < 9) issue_b((TAP + 2) % 3, TAP + 2, cc);
     else issue_b((TAP + 2) % 3, TAP + 2 - 9, b_ncc);
-    if (!SRCPP && !(ABL & 2) && TAP >= 2 && TAP - 2 < MAXP) convert_piece(pbuf ^ 1, TAP - 2);
+    if (!SRCPP && TAP >= 2 && TAP - 2 < MAXP) convert_piece(pbuf ^ 1, TAP - 2);
     const char* pb = lds + pbuf * PATCH_B;
     const char* sb = lds + (TAP % 3) * BSTAGE_B;
     bf16x8_t ah[TM], al[TM], bh[TN], bl[TN];
     int x16 = 16;                                       // opaque to the optimiser: keeps the 18 "lo" addresses out of registers
     asm volatile("" : "+s"(x16));
-    if (ABL & 8) {
-#pragma unroll
-      for (int t = 0; t < TM; ++t) { KEEP_OUT(ah[t]); KEEP_OUT(al[t]); }
-#pragma unroll
-      for (int u = 0; u < TN; ++u) { KEEP_OUT(bh[u]); KEEP_OUT(bl[u]); }
-    } else {
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       ah[t] = *reinterpret_cast<const bf16x8_t*>(pb + aoff[TAP][t]);
@@ -289,20 +262,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
       bh[u] = *reinterpret_cast<const bf16x8_t*>(sb + boff[u]);
       bl[u] = PROD == 0 ? *reinterpret_cast<const bf16x8_t*>(sb + (boff[u] ^ 16)) : bh[u];
     }
-    }
-    if (ABL & 4) {
-#pragma unroll
-      for (int t = 0; t < TM; ++t) { KEEP_IN(ah[t]); KEEP_IN(al[t]); }
-#pragma unroll
-      for (int u = 0; u < TN; ++u) { KEEP_IN(bh[u]); KEEP_IN(bl[u]); }
-    } else
 #pragma unroll
     for (int i = 0; i < nprod<PROD>() * TM * TN; ++i) {   // same product order as conv_patch_kernel
       const int grp = PROD == 0 ? i / (TM * TN) : 2, t = (i % (TM * TN)) / TN, u = i % TN;
-      // DIRECT: weights are the MFMA's row operand, pixels its columns: a lane ends up with 4 consecutive channels of ONE pixel
-      // per register quad and stores them itself (the same products summed over the same k order: bit-identical)
-      if (DIRECT) acc[t][u] = mma16<PROD>(grp == 1 ? bl[u] : bh[u], grp == 0 ? al[t] : ah[t], acc[t][u]);
-      else acc[t][u] = mma16<PROD>(grp == 0 ? al[t] : ah[t], grp == 1 ? bl[u] : bh[u], acc[t][u]);
+      acc[t][u] = mma16<PROD>(grp == 0 ? al[t] : ah[t], grp == 1 ? bl[u] : bh[u], acc[t][u]);
     }
   };
   // swapb: the B tiles fetched from tap 7 on belong to the next tile (nt; n0 < 0: there is none)
@@ -321,87 +284,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 
   // ---- epilogue of one tile: accumulators -> wave-private LDS (16 rows at a time) -> row-contiguous buffer stores ----
   const int flags = EPI >= 0 ? EPI : (g.flags & 0x3f);
-  auto epi_math = [&](float4 v, int dpix, int ns) {
-    if (flags & SRHIP_EPI_BIAS) {
-      const float4 bb = *reinterpret_cast<const float4*>(bias_s + ns);
-      v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-    }
-    if (flags & SRHIP_EPI_LRELU) {
-      v.x = v.x > 0.f ? v.x : v.x * g.slope;
-      v.y = v.y > 0.f ? v.y : v.y * g.slope;
-      v.z = v.z > 0.f ? v.z : v.z * g.slope;
-      v.w = v.w > 0.f ? v.w : v.w * g.slope;
-    }
-    if (flags & SRHIP_EPI_ACTMASK) {
-      const float4 a4 = *reinterpret_cast<const float4*>(actmask + (size_t)dpix * g.ldd + ns);
-      v.x = a4.x > 0.f ? v.x : v.x * g.slope;
-      v.y = a4.y > 0.f ? v.y : v.y * g.slope;
-      v.z = a4.z > 0.f ? v.z : v.z * g.slope;
-      v.w = a4.w > 0.f ? v.w : v.w * g.slope;
-    }
-    if (flags & SRHIP_EPI_RESIDUAL) {
-      const float4 r4 = *reinterpret_cast<const float4*>(residual + (size_t)dpix * g.ldr + ns);
-      v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
-    }
-    return v;
-  };
-  auto epilogue_direct = [&](const TileAt& t) {
-    if (ABL & 32) {
-#pragma unroll
-      for (int tt = 0; tt < TM; ++tt)
-#pragma unroll
-        for (int u = 0; u < TN; ++u) KEEP_IN(acc[tt][u]);
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(z, rs_d, F_OOB + 16u * i, 0, 0);
-      }
-      zero_acc();
-      return;
-    }
-    int ln = lane;                                      // opaque: per-tile addresses are recomputed, not kept in registers
-    asm volatile("" : "+v"(ln));
-    const int l31e = ln & 31, khe = ln >> 5;
-#pragma unroll
-    for (int tt = 0; tt < TM; ++tt) {
-      const int pt = pix_tab[wm * WTM + tt * 32 + l31e];
-      const int orow = pt >> 16, ocol = pt & 0xffff;
-      const int oh = t.oh0 + orow, ow = t.ow0 + ocol;
-      const bool okp = orow < pg.PH && oh < g.OH && ow < g.OW;
-      const int dpix = okp ? (t.img * g.Hd + oh) * g.Wd + ow : 0;
-      const int nb = t.n0 + wn * WTN + 4 * khe;
-#pragma unroll
-      for (int u = 0; u < TN; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                  // registers 4q .. 4q+3: channels u*32 + 8q + 4*khalf + 0..3
-          const int n = nb + u * 32 + 8 * q;
-          const bool ok = okp && n < g.K;
-          const int ns = ok ? n : 0;
-          float4 v = make_float4(acc[tt][u][4 * q], acc[tt][u][4 * q + 1], acc[tt][u][4 * q + 2], acc[tt][u][4 * q + 3]);
-          v = epi_math(v, dpix, ns);
-          const unsigned eoff = (ok && !(ABL & 1)) ? (unsigned)(dpix * g.ldd + n) * 4u : F_OOB + ((ABL & 1) ? 16u * (unsigned)((tt * TN + u) * 4 + q) : 0u);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_d, eoff, 0, 2);   // aux 2 = nt
-        }
-    }
-    zero_acc();
-  };
   auto epilogue = [&](const TileAt& t) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every wave's fragment reads of the last tap are done:
     __builtin_amdgcn_s_barrier();                        // its patch buffer and ring slot 2 are free
     asm volatile("" ::: "memory");
-    if (ABL & 32) {
-#pragma unroll
-      for (int t = 0; t < TM; ++t)
-#pragma unroll
-        for (int u = 0; u < TN; ++u) KEEP_IN(acc[t][u]);
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(z, rs_d, F_OOB + 16u * i, 0, 0);
-      }
-      zero_acc();
-      return;
-    }
     float* wl = reinterpret_cast<float*>(wave < 3 ? lds + PATCH_B + wave * STG_B : lds + RING0 + 2 * BSTAGE_B);   // the last chunk's buffer is 1
     int ln = lane;                                      // opaque: the per-pass addresses are recomputed per tile, not kept in registers
     asm volatile("" : "+v"(ln));
@@ -493,7 +379,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
             v.x += e4.x; v.y += e4.y; v.z += e4.z; v.w += e4.w;
           }
         }
-        const unsigned eoff = (ok && !(ABL & 1)) ? doff : F_OOB + ((ABL & 1) ? 16u * (unsigned)(p * NRD + i) : 0u);
+        const unsigned eoff = ok ? doff : F_OOB;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_d, eoff, 0, 2);   // aux 2 = nt
         if (POOL && ok) {                               // pixel index inside the image: the arg-max the backward scatters to
           const int pt = pix_tab[wm * WTM + (p >> 1) * 32 + (p & 1) * 16 + i * (64 / QPRW) + rsub];
@@ -688,15 +574,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 #pragma unroll
   for (int k = 0; k < MAXP; ++k) issue_a(0, k, 0u);
   issue_b(0, 0, 0);
-  if (XB == 2) issue_b(0, 0, 0);
   issue_b(1, 1, 0);
-  if (XB == 2) issue_b(1, 1, 0);
 #pragma unroll
   for (int i = 0; i < NS; ++i) {                    // NS dropped stores: the first tile's taps 0 and 1 count like every other tile's
     const u32x4 z = {0u, 0u, 0u, 0u};
     __builtin_amdgcn_raw_buffer_store_b128(z, rs_d, F_OOB + 16u * i, 0, 0);   // distinct offsets: identical stores would be merged
   }
-  wait_vmcnt<XB * BPW + NS>();
+  wait_vmcnt<BPW + NS>();
   if (!SRCPP) {
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) convert_piece(0, k);
@@ -713,7 +597,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     set_a(nxt);                                     // this tile's patches are all fetched: taps 0..2 fetch the next tile's first
     do_chunk(IC<0>(), IC<1>(), CC - 1, 0u, 0, true, nxt);
     if (DSTPP) epilogue_pp(cur);
-    else if (DIRECT) epilogue_direct(cur);
     else epilogue(cur);
     cur = nxt;
   }
@@ -727,7 +610,6 @@ int g_pool_epi_any = 1; // srhip_debug_set(19, 0): the CLAM pooling epilogue onl
                         // forward that pass is a launch of its own in a serial chain on the one stream that runs: +0.35 % of the step (profiles/r06_step_ab.txt)
 int g_pers_small = 1;   // srhip_debug_set(11, v): 0 = launches with fewer tiles than block slots keep the one-tile kernels
 int g_pers_grid = 0;      // srhip_debug_set(5, n)
-int g_pers_abl = 0;       // srhip_debug_set(6, bits): timing-only ablations of conv_patch_pers_kernel<128, bias+lrelu>
 static int g_num_cu = 0;
 static int num_cu() {
   if (g_num_cu == 0) {
@@ -771,7 +653,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
 #define SRHIP_PPX(BN_, EPI_, POOL_, SRC_, DST_, PO_, PS_)                                                                        \
   do {                                                                                                                           \
     if ((g.res2 || g.res3) && !(DST_)) g_res_req.served = 1;                                                                     \
-    hipLaunchKernelGGL((conv_patch_pers_kernel<BN_, EPI_, 0, 0, POOL_, SRC_, DST_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
+    hipLaunchKernelGGL((conv_patch_pers_kernel<BN_, EPI_, 0, POOL_, SRC_, DST_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
                        residual, actmask, dst, g, pg, nbm, nbn, pdbu, ndst16, PO_, PS_);                                         \
     return check_launch("conv_patch_pers_pp");                                                                                   \
   } while (0)
@@ -782,7 +664,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
       g_sign_req.served = 1;
 #define SRHIP_PPS(EPI_, SRC_, SG_)                                                                                              \
   do {                                                                                                                         \
-    hipLaunchKernelGGL((conv_patch_pers_kernel<128, EPI_, 0, 0, 0, SRC_, 1, SG_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
+    hipLaunchKernelGGL((conv_patch_pers_kernel<128, EPI_, 0, 0, SRC_, 1, SG_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
                        residual, words, dst, g, pg, nbm, nbn, pdbu, ndst16, nullptr, 0u);                                      \
     return check_launch("conv_patch_pers_pp_signs");                                                                           \
   } while (0)
@@ -870,23 +752,13 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
       const unsigned ps = g_pool_req.sec_bytes;
       g_pool_req.served_nseg = nseg;
       if (eflags == 0)
-        hipLaunchKernelGGL((conv_patch_pers_kernel<64, 0, 0, 0, 1>), dim3(grid), dim3(256), 0, st, src, wsplit, bias, residual, actmask, dst, g,
+        hipLaunchKernelGGL((conv_patch_pers_kernel<64, 0, 0, 1>), dim3(grid), dim3(256), 0, st, src, wsplit, bias, residual, actmask, dst, g,
                            pg, nbm, nbn, db, ndst16, po, ps);
       else
-        hipLaunchKernelGGL((conv_patch_pers_kernel<64, 1, 0, 0, 1>), dim3(grid), dim3(256), 0, st, src, wsplit, bias, residual, actmask, dst, g,
+        hipLaunchKernelGGL((conv_patch_pers_kernel<64, 1, 0, 1>), dim3(grid), dim3(256), 0, st, src, wsplit, bias, residual, actmask, dst, g,
                            pg, nbm, nbn, db, ndst16, po, ps);
       return check_launch("conv_patch_pers_pool");
     }
-  }
-  if (g_pers_abl != 0 && wide && prod == 0 && eflags == (SRHIP_EPI_BIAS | SRHIP_EPI_LRELU)) {
-#define SRHIP_PA(ABL_)                                                                                                  \
-  if (g_pers_abl == ABL_) {                                                                                             \
-    hipLaunchKernelGGL((conv_patch_pers_kernel<128, 3, 0, ABL_>), dim3(grid), dim3(256), 0, st, src, wsplit, bias,      \
-                       residual, actmask, dst, g, pg, nbm, nbn, db, ndst16, nullptr, 0u);                                                    \
-    return check_launch("conv_patch_pers");                                                                             \
-  }
-    SRHIP_PA(1) SRHIP_PA(2) SRHIP_PA(4) SRHIP_PA(12) SRHIP_PA(16) SRHIP_PA(32) SRHIP_PA(30) SRHIP_PA(26) SRHIP_PA(63) SRHIP_PA(64) SRHIP_PA(128) SRHIP_PA(256)
-#undef SRHIP_PA
   }
 #define SRHIP_PPE(BN_)                                                     \
   do {                                                                     \

@@ -463,8 +463,8 @@ struct WgradBatch {
   int nprob, bpp;
 };
 
-template <int BM, int CIS, bool SPLIT = true, int ADDR = 1, bool PIPE = false>     // SPLIT false: one bf16 product per multiply (SRHIP_MATH_HALF)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 3))) void wgrad_rowtap_kernel(
+template <int BM, int CIS, bool SPLIT = true>     // SPLIT false: one bf16 product per multiply (SRHIP_MATH_HALF)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void wgrad_rowtap_kernel(
     const float* __restrict__ x_, const float* __restrict__ dy_, float* __restrict__ partial_,
     float* __restrict__ bias_partial_, WgradGeom g, int nseg, int chunks_per_split, int tail_rem, WgradBatch bt) {
   const float* x = x_;
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
   constexpr int NBT = B_B / 1024;                   // B pieces per chunk, dealt to the waves in order
   constexpr int RPA = 1024 / (BM * 4), RPB = 1024 / (CIS * 4);   // pixel rows per piece
   constexpr int EPI_B = 4 * 32 * 32 * 4;
-  constexpr int NSLOT = PIPE ? 5 : 3;               // PIPE: two blocks per CU (registers), so the ring can be five chunks deep
+  constexpr int NSLOT = 3;
   constexpr int LDS_B = NSLOT * STAGE_B > EPI_B ? NSLOT * STAGE_B : EPI_B;
   __shared__ __attribute__((aligned(1024))) char lds[LDS_B];
 
@@ -545,9 +545,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
   const unsigned a_dst = __builtin_amdgcn_readfirstlane(lds_base + wave * NA * 1024);
   const unsigned b_dst = __builtin_amdgcn_readfirstlane(lds_base + A_B + b_first * 1024);
 
-  __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, g.x_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy), 0, g.dy_bytes, 0x00020000);
-  int i_n, i_ho, i_seg;                             // chunk the next issue() fetches (scalars); paired tails: (i_n, i_ho) = row A of the pair, i_seg = index inside the pair
+  int i_n, i_ho, i_seg;                             // chunk the next issue_s() fetches (scalars); paired tails: (i_n, i_ho) = row A of the pair, i_seg = index inside the pair
   if (tail_rem > 0) {
     i_seg = c_begin % cpp;
     const int r0 = (c_begin / cpp) * 2;
@@ -559,84 +558,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
     i_ho = t % g.Ho;
     i_n = t / g.Ho;
   }
-  auto issue_tail = [&](int slot) {                 // both rows' tails: pixel slots 0..7 <- row A, 8..15 <- row B
-    const int nB = i_ho + 1 < g.Ho ? i_n : i_n + 1, hoB = i_ho + 1 < g.Ho ? i_ho + 1 : 0;
-    const int wo0 = q * 16;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int j = (wave * NA + i) * RPA + a_rsub;
-      const int half = j >> 3, jj = j & 7;
-      const int n_ = half ? nB : i_n, ho_ = half ? hoB : i_ho;
-      const bool ok = a_colok && jj < tail_rem && n_ < g.N;
-      const unsigned off = ok ? (unsigned)((((long)n_ * g.Ho + ho_) * g.Wo + wo0 + jj) * g.ldy + m0 + a_col * 4) * 4u : F_OOB;
-      lds_dma16_buf(off, rs_y, a_dst + slot * STAGE_B + i * 1024);
-    }
-#pragma unroll
-    for (int i = 0; i < NBT / 4 + 1; ++i) {
-      if (i < nb) {
-        const int r = (b_first + i) * RPB + b_rsub;            // staged row 0..19: half = r >= 10
-        const int half = r >= 10 ? 1 : 0, ss = r - 10 * half;
-        const int n_ = half ? nB : i_n, ho_ = half ? hoB : i_ho;
-        const int hi = ho_ - 1 + kh, wi = wo0 - 1 + ss;
-        const bool ok = n_ < g.N && hi >= 0 && hi < g.H && ss < tail_rem + 2 && wi < g.W;
-        lds_dma16_buf(ok ? (unsigned)((((long)n_ * g.H + hi) * g.W + wi) * g.ldx + ci_base + b_col * 4) * 4u : F_OOB, rs_x, b_dst + slot * STAGE_B + i * 1024);
-      }
-    }
-  };
-  auto issue = [&](int slot) {
-    if (tail_rem > 0) {
-      if (i_seg == 2 * q) {
-        issue_tail(slot);
-        i_seg = 0;
-        i_ho += 2;
-        if (i_ho >= g.Ho) {
-          i_ho -= g.Ho;
-          ++i_n;
-        }
-        return;
-      }
-    }
-    const bool rowB = tail_rem > 0 && i_seg >= q;
-    const int c_n = rowB ? (i_ho + 1 < g.Ho ? i_n : i_n + 1) : i_n;
-    const int c_ho = rowB ? (i_ho + 1 < g.Ho ? i_ho + 1 : 0) : i_ho;
-    const bool rowlive = c_n < g.N;                  // odd row count: the last pair has no row B
-    const int wo0 = (rowB ? i_seg - q : i_seg) * 16;
-    const long prow = ((long)c_n * g.Ho + c_ho) * g.Wo + wo0;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int j = (wave * NA + i) * RPA + a_rsub;            // output pixel slot 0..15
-      const unsigned off = (a_colok && rowlive && wo0 + j < g.Wo) ? (unsigned)((prow + j) * g.ldy + m0 + a_col * 4) * 4u : F_OOB;
-      lds_dma16_buf(off, rs_y, a_dst + slot * STAGE_B + i * 1024);   // out of range => the hardware writes zeros
-    }
-    const int hi = c_ho - 1 + kh;
-    const bool rowok = rowlive && hi >= 0 && hi < g.H;
-    const long xrow = ((long)c_n * g.H + hi) * g.W;
-#pragma unroll
-    for (int i = 0; i < NBT / 4 + 1; ++i) {
-      if (i < nb) {
-        const int r = (b_first + i) * RPB + b_rsub;            // staged pixel row: input column wo0 - 1 + r
-        const int wi = wo0 - 1 + r;
-        const bool ok = rowok && r < 18 && wi >= 0 && wi < g.W;
-        lds_dma16_buf(ok ? (unsigned)((xrow + wi) * g.ldx + ci_base + b_col * 4) * 4u : F_OOB, rs_x, b_dst + slot * STAGE_B + i * 1024);
-      }
-    }
-    if (tail_rem > 0) {
-      ++i_seg;                                      // the tail chunk (i_seg == 2 q) closes the pair
-    } else if (++i_seg == nseg) {
-      i_seg = 0;
-      if (++i_ho == g.Ho) {
-        i_ho = 0;
-        ++i_n;
-      }
-    }
-  };
-  // ADDR 1 (round 4): the same DMAs with the chunk's position as the instruction's SCALAR offset.  The form above rebuilds every
-  // lane's byte offset per chunk (64-bit pixel arithmetic, selects lowered to exec-mask branches: ~90 VALU instructions and 16
-  // branches per chunk and wave in front of the 18 MFMAs).  Here a lane keeps constant offsets relative to the chunk's first
-  // pixel, the chunk's first pixel goes into the buffer instruction's soffset (tensors < 2 GiB, so offset + soffset cannot wrap
-  // and a dead lane's 0x80000000 stays out of range whichever way the range check counts soffset), and validity is one
-  // compare against a scalar limit.  The x descriptor starts one image row + one pixel BEFORE the tensor so that the halo
-  // pixel (-1) of row -1 has offset 0; lanes that would read there are dead lanes.  Same bytes into the same LDS places.
+  // The DMAs take the chunk's position as the instruction's SCALAR offset (round 4; rounds 1-3 rebuilt every lane's byte offset
+  // per chunk: ~90 VALU instructions and 16 branches per chunk and wave in front of the 18 MFMAs).  A lane keeps constant
+  // offsets relative to the chunk's first pixel, the chunk's first pixel goes into the buffer instruction's soffset (tensors
+  // < 2 GiB, so offset + soffset cannot wrap and a dead lane's 0x80000000 stays out of range whichever way the range check
+  // counts soffset), and validity is one compare against a scalar limit.  The x descriptor starts one image row + one pixel
+  // BEFORE the tensor so that the halo pixel (-1) of row -1 has offset 0; lanes that would read there are dead lanes.
   const unsigned x_shift = (unsigned)(g.W + 1) * (unsigned)g.ldx * 4u;
   __amdgpu_buffer_rsrc_t rs_xs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) - (size_t)(g.W + 1) * g.ldx, 0, g.x_bytes + x_shift, 0x00020000);
   unsigned a_full[NA], a_tailv[NA], a_tailA[NA];     // dy: full chunk / tail chunk (both rows live) / tail chunk (row B dead)
@@ -664,8 +591,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
     const bool okss = r < 20 && ss <= tail_rem && wo0t - 1 + ss >= 0;            // input column wo0 - 1 + ss inside the row
     b_tailv[i] = okss ? (unsigned)((half * g.W + ss) * g.ldx + ci_base + b_col * 4) * 4u : F_OOB;
   }
-  int i_row = 0;                                    // flat output row (image * Ho + row) of the chunk the next issue fetches (row A of a pair)
-  if (ADDR == 1) i_row = i_n * g.Ho + i_ho;
+  int i_row = i_n * g.Ho + i_ho;                    // flat output row (image * Ho + row) of the chunk the next issue fetches (row A of a pair)
   const int rows_all = g.N * g.Ho;
   auto dma_s = [&](unsigned voff, unsigned soff, __amdgpu_buffer_rsrc_t r, unsigned dst) {
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(r), "s"(soff), "s"(dst) : "memory");
@@ -745,10 +671,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
   float bsum = 0.f;
   const bool want_bias = bias_partial != nullptr && tile_n == 0 && tid < BM;
 
-  auto issue_any = [&](int slot) {
-    if (ADDR == 1) issue_s(slot);
-    else issue(slot);
-  };
   struct Frags {
     bf16x8_t ah[TM], al[TM], bh[TN], bl[TN];
   };
@@ -801,76 +723,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE ? 2 : 
       acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(grp == 0 ? f.al[t] : f.ah[t], grp == 1 ? f.bl[u] : f.bh[u], acc[t][u], 0, 0, 0);
     }
   };
-  if constexpr (!PIPE) {
-    if (nk > 0) {
-      issue_any(0);
-      if (nk > 1) issue_any(1);
-      int stage = 0, nstage = 2;
-      for (int kc = 0; kc < nk; ++kc) {
-        wait_chunk(kc + 1 < nk);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kc + 2 < nk) issue_any(nstage);
-        Frags f;
-        convert(stage, f);
-        mfma_all(f);
-        stage = stage == 2 ? 0 : stage + 1;
-        nstage = nstage == 2 ? 0 : nstage + 1;
-      }
-    }
-  } else {
-    // PIPE (round 4): the conversion of chunk k + 1 and the MFMAs of chunk k are independent instruction streams of one loop body.
-    // In the form above a wave alternates a ~90-instruction gather / split phase with 18 back-to-back MFMAs, and the co-resident
-    // waves of a SIMD (same code, started together, re-synchronised by every stall) do the same phases at the same time: the
-    // ablation of round 2 found the parts ADDING UP (MFMAs 37, conversion 24, DMA 7, barrier 4.5 of 123 us).  Holding the next
-    // chunk's fragments costs 40 registers: two waves per SIMD instead of three, which pays for a five-deep operand ring.
-    constexpr int D = NSLOT - 1;                    // chunks in flight
-    const int per = NA + nb;                        // DMAs of this wave per chunk
-    auto wait_after = [&](int chunks) {             // all but the newest `chunks` chunks of this wave's DMAs have landed
-      const int n = chunks * per;
-      switch (n) {
-        case 0: wait_vmcnt<0>(); break;
-        case 3: wait_vmcnt<3>(); break;
-        case 4: wait_vmcnt<4>(); break;
-        case 6: wait_vmcnt<6>(); break;
-        case 8: wait_vmcnt<8>(); break;
-        case 9: wait_vmcnt<9>(); break;
-        case 12: wait_vmcnt<12>(); break;
-        default: wait_vmcnt<0>(); break;
-      }
-    };
-    static_assert(NA + NBT / 4 == 3, "wait_after's cases assume 3 or 4 DMAs per wave and chunk");
-    if (nk > 0) {
-      int issued = 0;
-      for (; issued < D && issued < nk; ++issued) issue_any(issued);
-      wait_after(issued - 1);
+  if (nk > 0) {
+    issue_s(0);
+    if (nk > 1) issue_s(1);
+    int stage = 0, nstage = 2;
+    for (int kc = 0; kc < nk; ++kc) {
+      wait_chunk(kc + 1 < nk);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      int islot = D;
-      if (issued < nk) {
-        issue_any(islot);
-        ++issued;
-        islot = 0;
-      }
+      if (kc + 2 < nk) issue_s(nstage);
       Frags f;
-      convert(0, f);
-      int cslot = 1;
-      for (int kc = 0; kc + 1 < nk; ++kc) {
-        wait_after(issued - (kc + 2));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (issued < nk) {
-          issue_any(islot);
-          ++issued;
-          islot = islot == NSLOT - 1 ? 0 : islot + 1;
-        }
-        Frags gnext;
-        convert(cslot, gnext);
-        mfma_all(f);
-        f = gnext;
-        cslot = cslot == NSLOT - 1 ? 0 : cslot + 1;
-      }
+      convert(stage, f);
       mfma_all(f);
+      stage = stage == 2 ? 0 : stage + 1;
+      nstage = nstage == 2 ? 0 : nstage + 1;
     }
   }
 
@@ -1133,8 +999,6 @@ __global__ __launch_bounds__(256) void wgrad_1x1_scaled_kernel(const float* __re
 struct FastWgradPlan {
   int bm, bn, bk, nsplit, chunks_per_split;
 };
-int g_rowtap_pipe = 0; // srhip_debug_set(9, v): 1 = software-pipelined row-tap kernel (conversion of chunk k+1 beside the MFMAs of chunk k, 2 blocks / CU)
-int g_rowtap_addr = 1; // srhip_debug_set(8, v): 0 = per-lane DMA offsets of rounds 1-3 in wgrad_rowtap_kernel (A/B), 1 = scalar chunk offsets
 int g_wgrad_cfg = 0;   // srhip_debug_set(1, cfg): a WgradCfg value (conv_dev.h), 0 = the heuristic
 // row-tap kernel (wgrad_rowtap_kernel): split-bf16, 3x3 stride 1 pad 1, Cin % 64 == 0, Cout % 4 == 0
 static int rowtap_ok(int cin, int cout, int kh, int kw, int stride, int pad) {   // 0: no, 1: 128 x (kh, 64 ci), 2: 64 x (kh, 128 ci)
@@ -1206,7 +1070,7 @@ static int multi_nsplit(const FastWgradPlan& p, int nprob) {
 
 enum class WgradFamily {
   Tail1x1,   // wgrad_1x1_scaled_kernel
-  RowTap,    // wgrad_rowtap_kernel<bm, cis, split, addr, pipe>, one problem or a group of nprob
+  RowTap,    // wgrad_rowtap_kernel<bm, cis, split>, one problem or a group of nprob
   Dma,       // fast_wgrad_dma_kernel<bm, bn, wm, wn, wbk, math>
   Reg,       // fast_wgrad_kernel<bm, bn, wm, wn>: operand scales, or g_wgrad_cfg >= 10
 };
@@ -1216,8 +1080,6 @@ struct WgradRoute {
   int nsplit = 0, cps = 0;    // splits per problem and chunks per split as the kernel walks them (what WgradGeom carries)
   int rowtap = 0;             // RowTap: 1 = 128 x (kh, 64 ci), 2 = 64 x (kh, 128 ci)
   bool split = true;          // RowTap: split-bf16 (false: one bf16 product, SRHIP_MATH_HALF)
-  int addr = 1;               // RowTap: ADDR template argument (g_rowtap_addr)
-  bool pipe = false;          // RowTap: software-pipelined form (g_rowtap_pipe)
   int nseg = 0, tail_rem = 0; // RowTap: 16-pixel segments per image row, paired-tail remainder (0: none)
   int wbk = 16, math = 0;     // Dma: pixels per K chunk, arithmetic (0 fp32, 1 split-bf16, 2 one bf16 product)
   int sp = 0, per = 0;        // Tail1x1: splits per image, pixels per split
@@ -1244,8 +1106,6 @@ static WgradRoute choose_wgrad_route(const WgradGeom& g, int nprob, bool xrow, b
   } else if (r.rowtap) {
     r.family = WgradFamily::RowTap;
     r.split = g_conv_math != 2;
-    r.pipe = g_rowtap_pipe != 0;
-    r.addr = (r.pipe || g_rowtap_addr) ? 1 : 0;
     r.nseg = cdiv(g.Wo, 16);
     // paired tails (see the kernel): rows of 16 q + rem pixels, 0 < rem <= 8, at least two rows per image
     const int rem = g.Wo & 15;
@@ -1263,8 +1123,7 @@ static WgradRoute choose_wgrad_route(const WgradGeom& g, int nprob, bool xrow, b
 template <int BM, int CIS>
 static void launch_rowtap(const WgradRoute& r, const WgradGeom& g, const float* x, const float* dy, float* partial, float* bias_partial,
                           const WgradBatch& bt, int blocks, hipStream_t st) {
-  auto k = r.split ? (r.pipe ? wgrad_rowtap_kernel<BM, CIS, true, 1, true> : r.addr ? wgrad_rowtap_kernel<BM, CIS, true, 1> : wgrad_rowtap_kernel<BM, CIS, true, 0>)
-                   : (r.pipe ? wgrad_rowtap_kernel<BM, CIS, false, 1, true> : r.addr ? wgrad_rowtap_kernel<BM, CIS, false, 1> : wgrad_rowtap_kernel<BM, CIS, false, 0>);
+  auto k = r.split ? wgrad_rowtap_kernel<BM, CIS, true> : wgrad_rowtap_kernel<BM, CIS, false>;
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, x, dy, partial, bias_partial, g, r.nseg, r.cps, r.tail_rem, bt);
 }
 template <int BM, int BN, int WM, int WN>

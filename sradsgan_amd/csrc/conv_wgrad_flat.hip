@@ -63,20 +63,14 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
 
-template <int ABL = 0>
+// 8 K values (two transposing reads, 4 pixel rows each) of this lane's channel
 __device__ __forceinline__ bf16x8_t tr_frag(unsigned addr) {
-  if (ABL & 4) {
-    bf16x8_t z;
-    asm volatile("" : "=v"(z) : "v"(addr));
-    return z;
-  }      // 8 K values (two transposing reads, 4 pixel rows each) of this lane's channel
   const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(addr));
   const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(addr + 1024));     // + 4 rows of 256 B
   return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// ABL: timing-only ablations (wrong results; srhip_debug_set(13, bits)): 1 no MFMAs, 2 no DMAs, 4 no fragment reads, 8 no partial stores, 16 no in-place split
-template <int CFG, int ABL = 0>
+template <int CFG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void wgrad_flat_kernel(FlatGeom g, FlatBatch bt) {
   static_assert(CFG == 1 || CFG == 2, "two tile shapes");
   constexpr int BM = CFG == 1 ? 128 : 64, CIS = CFG == 1 ? 64 : 128;
@@ -182,7 +176,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
     f_pix[k] = (f_n[k] * g.H + f_h[k]) * g.W + f_w[k];
   }
   auto dma_s = [&](unsigned voff, unsigned soff, __amdgpu_buffer_rsrc_t r, unsigned dst) {
-    if (ABL & 2) voff = F_OOB;
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(r), "s"(soff), "s"(dst) : "memory");
   };
   int c_issue = c_begin;
@@ -325,28 +318,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
       bf16x8_t ah[TM], al[TM];
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
-        ah[t] = tr_frag<ABL>(sb + a_hi[t]);
-        al[t] = tr_frag<ABL>(sb + (CFG == 1 ? a_hi[t] + A_LO : a_hi[t] ^ 8u));
+        ah[t] = tr_frag(sb + a_hi[t]);
+        al[t] = tr_frag(sb + (CFG == 1 ? a_hi[t] + A_LO : a_hi[t] ^ 8u));
       }
       // tap by tap (kw = u): two x fragments live at a time; the three products of an accumulator tile keep the order al*bh, ah*bl, ah*bh
 #pragma unroll
       for (int u = 0; u < TN; ++u) {
-        const bf16x8_t bh = tr_frag<ABL>(sb + b_hi[u]);
-        const bf16x8_t bl = tr_frag<ABL>(sb + (CFG == 2 ? b_hi[u] + B_LO : b_hi[u] ^ 8u));
+        const bf16x8_t bh = tr_frag(sb + b_hi[u]);
+        const bf16x8_t bl = tr_frag(sb + (CFG == 2 ? b_hi[u] + B_LO : b_hi[u] ^ 8u));
         if (u == 1 && kc + 1 < nk) {                         // the next chunk's fp32 pieces: landed by now, split between the taps
           wait_newer(min(nk - (kc + 2), 2));
-          if (!(ABL & 16)) convert((kc + 1) & 3);
+          convert((kc + 1) & 3);
         }
-        if (ABL & 1) {
-          asm volatile("" ::"v"(bh), "v"(bl), "v"(ah[0]), "v"(al[0]), "v"(ah[1]), "v"(al[1]));
-        } else {
 #pragma unroll
-          for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][u], 0, 0, 0);
+        for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh, acc[t][u], 0, 0, 0);
 #pragma unroll
-          for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl, acc[t][u], 0, 0, 0);
+        for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl, acc[t][u], 0, 0, 0);
 #pragma unroll
-          for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bh, acc[t][u], 0, 0, 0);
-        }
+        for (int t = 0; t < TM; ++t) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bh, acc[t][u], 0, 0, 0);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -372,7 +361,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
         const float4 v = *reinterpret_cast<const float4*>(wl + row * 32 + cq * 4);
         const int m = m0 + wm * 64 + t * 32 + row;
         const int n = (kh * 3 + u) * g.C + ci_base + wn * 32 + cq * 4;
-        if (m < g.K && !(ABL & 8)) *reinterpret_cast<float4*>(out + (size_t)m * g.Ktot + n) = v;
+        if (m < g.K) *reinterpret_cast<float4*>(out + (size_t)m * g.Ktot + n) = v;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -414,7 +403,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
 // chunk loop ONE BARRIER APART -- while group 0 multiplies chunk c (18 MFMAs per wave, matrix pipe only), group 1 issues its DMAs and
 // reads its fragments of chunk c (memory / LDS pipes only), then they swap (the guide's 256^2 8-phase GEMM template, section 5).
 // The 4-wave form above has every wave alternate load and multiply phases itself, three lock-stepped blocks per CU: its ablations
-// (tools/ablate_wgrad_flat.py) show the phases ADDING UP -- MFMAs 72 us, DMA issue 47, fragment reads 40, in-place split 28, loop
+// (profiles/r05_wgrad_flat_ablations.txt) showed the phases ADDING UP -- MFMAs 72 us, DMA issue 47, fragment reads 40, in-place split 28, loop
 // skeleton 36 of 182 -- because co-resident waves run the same phase at the same time.  Here the two waves of a SIMD are in opposite
 // phases by construction.
 //   CFG 1: block = 256 co x (kh, 3 kw, 64 ci): group g owns co [128 g, 128 g + 128); dy = planes [., K], x = planes [., C] (64-ch slice)
@@ -432,7 +421,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
 // the wave that fetched it, one chunk ahead of its first reader, inside the load phase (the 4-wave form's image: 256-byte rows,
 // 16-byte granule = [4 hi | 4 lo], odd rows [lo | hi], 128-byte halves swapped when (row >> 1) & 1).  Saves the stand-alone pp_from_f32
 // pass (24 MB read + 24 MB written per operand) the step would otherwise run for the block input x and the tail's gradient du.
-template <int CFG, int ABL = 0, int F32 = 0>
+template <int CFG, int F32 = 0>
 __global__ __launch_bounds__(512) void wgrad_flat8_kernel(FlatGeom g, FlatBatch bt) {
   static_assert(CFG == 1 || CFG == 2, "two tile shapes");
   constexpr int TM = 2, TN = 3;
@@ -568,7 +557,6 @@ __global__ __launch_bounds__(512) void wgrad_flat8_kernel(FlatGeom g, FlatBatch 
     if (f_wave) d_dst[2] = __builtin_amdgcn_readfirstlane(lds_base + (CFG == 1 ? A_B : 0) + wave * 1024);
   }
   auto dma_s = [&](unsigned voff, unsigned soff, __amdgpu_buffer_rsrc_t r, unsigned dst) {
-    if (ABL & 2) voff = F_OOB;
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(r), "s"(soff), "s"(dst) : "memory");
   };
   const unsigned yC2 = (unsigned)g.K * 4u, xC2 = (unsigned)g.C * 4u;     // bytes per pixel row of the padded tensors
@@ -630,11 +618,6 @@ __global__ __launch_bounds__(512) void wgrad_flat8_kernel(FlatGeom g, FlatBatch 
     }
   }
   auto frag = [&](unsigned addr, int r4) {                   // two transposing reads, 4 pixel rows apart
-    bf16x8_t z;
-    if (ABL & 4) {
-      asm volatile("" : "=v"(z) : "v"(addr));
-      return z;
-    }
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(addr));
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(addr + r4));
     return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -738,20 +721,13 @@ __global__ __launch_bounds__(512) void wgrad_flat8_kernel(FlatGeom g, FlatBatch 
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     // ---- multiply phase (the other group loads)
-    if (!(ABL & 1)) {
-      __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int i = 0; i < 3 * TM * TN; ++i) {
-        const int pr = i / (TM * TN), t = (i % (TM * TN)) / TN, u = i % TN;
-        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pr == 0 ? al[t] : ah[t], pr == 1 ? bl[u] : bh[u], acc[t][u], 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-    } else {
-#pragma unroll
-      for (int t = 0; t < TM; ++t) asm volatile("" ::"v"(ah[t]), "v"(al[t]));
-#pragma unroll
-      for (int u = 0; u < TN; ++u) asm volatile("" ::"v"(bh[u]), "v"(bl[u]));
+    for (int i = 0; i < 3 * TM * TN; ++i) {
+      const int pr = i / (TM * TN), t = (i % (TM * TN)) / TN, u = i % TN;
+      acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pr == 0 ? al[t] : ah[t], pr == 1 ? bl[u] : bh[u], acc[t][u], 0, 0, 0);
     }
+    __builtin_amdgcn_s_setprio(0);
     if (!F32 && grp == 0) wait_vmcnt<6>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -782,7 +758,7 @@ __global__ __launch_bounds__(512) void wgrad_flat8_kernel(FlatGeom g, FlatBatch 
         const float4 v = *reinterpret_cast<const float4*>(wl + row * 32 + cq * 4);
         const int m = m0 + (CFG == 1 ? 128 * grp : 0) + wm * 64 + t * 32 + row;
         const int n = (kh * 3 + u) * g.C + ci_base + (CFG == 2 ? 128 * grp : 0) + wn * 32 + cq * 4;
-        if (m < g.K && !(ABL & 8)) *reinterpret_cast<float4*>(out + (size_t)m * g.Ktot + n) = v;
+        if (m < g.K) *reinterpret_cast<float4*>(out + (size_t)m * g.Ktot + n) = v;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -872,7 +848,6 @@ __global__ __launch_bounds__(256) void pp_to_f32_kernel(const __bf16* __restrict
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------- //
-int g_flat_abl = 0;         // srhip_debug_set(13, bits): timing-only ablations of wgrad_flat_kernel
 int g_flat_f32_k8 = 1;      // srhip_debug_set(14, v): 0 = one fp32 operand always takes the 4-wave kernel (1: the 8-wave kernel where its tile fits)
 int g_flat_blocks = 768;      // srhip_debug_set(12, n): split-K block target of wgrad_flat_kernel
 bool launch_reduce4_shared(int nprob, const float* const* partial, const float* const* bias_partial, float* const* dw, float* const* db,
@@ -1013,26 +988,12 @@ int flat_wgrad(int nprob, const void* const* x, const void* const* dy, int x_pp,
   const int blocks = bt.bpp * nprob;
   const int cfg = p.cfg;
   if (p.kernel == 8) {
-#define SRHIP_F8(ABL_)                                                                                       \
-  if (g_flat_abl == ABL_) {                                                                                 \
-    if (cfg == 1) hipLaunchKernelGGL((wgrad_flat8_kernel<1, ABL_>), dim3(blocks), dim3(512), 0, st, g, bt);  \
-    else hipLaunchKernelGGL((wgrad_flat8_kernel<2, ABL_>), dim3(blocks), dim3(512), 0, st, g, bt);           \
-  } else
-    SRHIP_F8(1) SRHIP_F8(2) SRHIP_F8(4) SRHIP_F8(8) SRHIP_F8(3) SRHIP_F8(5) SRHIP_F8(6) SRHIP_F8(7) SRHIP_F8(15)
-#undef SRHIP_F8
     if (!(x_pp && dy_pp)) {
-      if (cfg == 1) hipLaunchKernelGGL((wgrad_flat8_kernel<1, 0, 1>), dim3(blocks), dim3(512), 0, st, g, bt);
-      else hipLaunchKernelGGL((wgrad_flat8_kernel<2, 0, 1>), dim3(blocks), dim3(512), 0, st, g, bt);
+      if (cfg == 1) hipLaunchKernelGGL((wgrad_flat8_kernel<1, 1>), dim3(blocks), dim3(512), 0, st, g, bt);
+      else hipLaunchKernelGGL((wgrad_flat8_kernel<2, 1>), dim3(blocks), dim3(512), 0, st, g, bt);
     } else if (cfg == 1) hipLaunchKernelGGL((wgrad_flat8_kernel<1>), dim3(blocks), dim3(512), 0, st, g, bt);
     else hipLaunchKernelGGL((wgrad_flat8_kernel<2>), dim3(blocks), dim3(512), 0, st, g, bt);
   } else {
-#define SRHIP_FA(ABL_)                                                                                   \
-  if (g_flat_abl == ABL_) {                                                                             \
-    if (cfg == 1) hipLaunchKernelGGL((wgrad_flat_kernel<1, ABL_>), dim3(blocks), dim3(256), 0, st, g, bt); \
-    else hipLaunchKernelGGL((wgrad_flat_kernel<2, ABL_>), dim3(blocks), dim3(256), 0, st, g, bt);          \
-  } else
-    SRHIP_FA(1) SRHIP_FA(2) SRHIP_FA(4) SRHIP_FA(8) SRHIP_FA(16) SRHIP_FA(3) SRHIP_FA(5) SRHIP_FA(6) SRHIP_FA(7) SRHIP_FA(31) SRHIP_FA(23)
-#undef SRHIP_FA
     if (cfg == 1) hipLaunchKernelGGL((wgrad_flat_kernel<1>), dim3(blocks), dim3(256), 0, st, g, bt);
     else hipLaunchKernelGGL((wgrad_flat_kernel<2>), dim3(blocks), dim3(256), 0, st, g, bt);
   }

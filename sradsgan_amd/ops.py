@@ -827,7 +827,6 @@ _WGRAD_MAX_AGE = 14    # weight-gradient calls a launch may wait for a partner
 # block per CU, so every convolution gets a third instead of half of the split-K splits (28 instead of 42): a third fewer partial tiles written and
 # reduced, and the launches line up with the group boundaries the exchange's parts are cut at.  +0.5 % same-box (profiles/r06_step_ab.txt; 4: the same)
 _PP_GROUP = 3
-_WGRAD_SLOTS = os.environ.get('SRHIP_WGRAD_SLOTS', '0') == '1'     # experiment, OFF: see _WgradQueue.release (kernel-level effect as predicted, step unchanged)
 
 
 class _Wgrad(NamedTuple):
@@ -854,9 +853,7 @@ class _WgradQueue:
         self.side = side
         self.capturing = _state.capturing               # (a stream capture wraps the whole context: TrainStep._capture)
         self.group = group if side is not None else 1   # weight gradients of one shape launched together (srhip_conv2d_wgrad_multi); 1 = off
-        self.slots = _WGRAD_SLOTS and not self.capturing   # complete plane launches wait for their slot (release)
         self.pending = {}                               # shape key -> [_Wgrad] waiting for partners
-        self.ready = []                                 # complete plane launches waiting for their slot
         self.held = []                                  # gradients kept referenced until the backward ends, see _passed_through
         self.seq = 0                                    # weight-gradient requests so far
 
@@ -935,12 +932,6 @@ class _WgradQueue:
         q = self.pending.setdefault(key, [])
         q.append(job)
         if len(q) >= group:
-            self.complete(key)
-
-    def complete(self, key):
-        if self.slots and key[0] == 'pp':
-            self.ready.append(self.pending.pop(key))      # goes out at the next slot (release)
-        else:
             self.flush(key)
 
     def flush(self, key):
@@ -949,34 +940,8 @@ class _WgradQueue:
             (self.run_planes if key[0] == 'pp' else self.run_fp32)(jobs)
 
     def flush_all(self):
-        self.release(len(self.ready))
         for key in list(self.pending):
             self.flush(key)
-
-    def release(self, n=1):
-        """Round 6: WHEN a complete pair of RAB weight gradients starts.  The 8-wave flat kernel holds one block on every CU for ~150 us
-        (2 x 170 of the 512 registers per SIMD lane) and leaves room for ONE block of a main-stream conv beside it.  The 128-wide conv
-        kernels live with that (12 MFMAs per barrier and wave: 87 us in the step against 79 alone); the 64-wide one -- conv1's data gradient,
-        256 -> 64, 6 MFMAs per barrier -- does not: 149 us in the step against 77 alone, 36 times per step on the main stream's chain
-        (profiles/r06_step_eager_kernel_stats.txt).  And the round-5 request order put the two exactly on top of each other: conv2's
-        weight gradient was requested between conv2's and conv1's data gradient, so a pair that completed there started the moment
-        conv1's data gradient did.  Now complete pairs wait in `ready` and ONE goes out right after every conv1 data gradient
-        has been enqueued (_RabBlock._backward_planes): it runs beside the next block's attention tail (streaming passes) and conv2 data
-        gradient (128-wide) -- ~210 us, room for one pair -- and is mostly done when the next conv1 data gradient starts.  Same kernels,
-        same accumulation order per parameter: bit-identical.
-        MEASURED (profiles/r06_step_ab.txt): conv1's data gradient 147.7 -> 91.6 us in the step, exactly as intended -- and the step does not
-        move (668.8 / 672.3 / 671.1 against 669.5 / 672.1 / 671.0 img/s): the tail's 1x1 data gradient (39 -> 48 us), the split-K reduces
-        (23 -> 31) and the 1x1 weight gradients (35 -> 40) take up what it gives back.  During the backward the chip's throughput is the limit,
-        not any kernel's place in a queue.  Kept as an option (SRHIP_WGRAD_SLOTS=1), off by default."""
-        for jobs in self.ready[:n]:
-            self.run_planes(jobs)
-        del self.ready[:n]
-
-
-def release_ready_pair(n=1):
-    """One complete launch of RAB weight gradients that waits for its slot goes out now (_WgradQueue.release, SRHIP_WGRAD_SLOTS=1)."""
-    if _state.wgrads is not None:
-        _state.wgrads.release(n)
 
 
 def flush_pending_pp():
@@ -984,13 +949,12 @@ def flush_pending_pp():
     q = _state.wgrads
     if q is not None:
         for key in [k for k in q.pending if k[0] == 'pp']:
-            q.complete(key)
+            q.flush(key)
 
 
 def flush_pending_wgrads():
-    """Launches every weight gradient that is still waiting for a partner of its shape (and every complete pair that is waiting for
-    its slot).  Called wherever something is about to order itself behind "all weight gradients so far": the exchange, the joins of
-    the step, the end of direct_param_grads()."""
+    """Launches every weight gradient that is still waiting for a partner of its shape.  Called wherever something is about to
+    order itself behind "all weight gradients so far": the exchange, the joins of the step, the end of direct_param_grads()."""
     if _state.wgrads is not None:
         _state.wgrads.flush_all()
 
@@ -1699,20 +1663,12 @@ class _RabBlock(Function):
         dw2 = db2 = dw1 = db1 = None
         main = torch.cuda.current_stream()
         t_done = dt_done = False
-        q = _state.wgrads
-        slots = q is not None and q.slots
-
-        def conv1_dgrad():                                # + skip gradient (+ the input's stashed gradients)
-            return conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None
-        if slots:                                         # conv1's data gradient FIRST, then one waiting launch of weight gradients (_WgradQueue.release)
-            dx = conv1_dgrad()
-            q.release(1)
+        # (request order: conv1's data gradient first, weight gradients held back for a slot behind it, did not move the step: DESIGN.md, profiles/r06_step_ab.txt)
         if not skip:
             t_done = wgrad_pp_for_params(w2, b2, t_pp, du_pp, ctx.has_b[1], release=(t_pp, du_pp))
             if not t_done:                                # autograd wants the gradients returned: the fp32 path on converted operands
                 dw2, db2 = wgrad_for_params(w2, b2, pp_to_f32(t_pp), pp_to_f32(du_pp), 1, 1, ctx.has_b[1])
-        if not slots:
-            dx = conv1_dgrad()
+        dx = conv2d_dgrad_pp_raw(dt_pp, w1, residual=g, extra=_carry_take(ctx.carry)) if ctx.needs_input_grad[0] else None   # + skip gradient (+ the input's stashed gradients)
         if not skip:
             dt_done = wgrad_pp_for_params(w1, b1, x_pp if x_pp is not None else x, dt_pp, ctx.has_b[0],
                                           release=(dt_pp,) if x_pp is None else (dt_pp, x_pp))
@@ -1725,8 +1681,6 @@ class _RabBlock(Function):
             plane_pool.put(dt_pp, (main,))
             if x_pp is not None:
                 plane_pool.put(x_pp, (main,))
-        if slots and x_pp is None:                        # the trunk's first block = the backward's last: no further slot will come
-            q.release(len(q.ready))
         if ctx.group_first:
             flush_pending_pp()                            # a launch never straddles ResGroups: what the exchange's group-boundary flush finds is the same with and without it
         return dx, dw1, db1, dw2, db2, dfc1, dfc2, dw7, dwc, dbc, None, None, None, None

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
 U = E.U24
 TAU = {'fp32': 32 * U, 'bf16x3': 20 * U, 'bf16': 20 * U, 'fp16': 20 * U}
-KNOB_DEFAULTS = {0: 0, 1: 0, 5: 0, 8: 1, 9: 0, 10: 1, 11: 1, 15: 0, 17: 1}
+KNOB_DEFAULTS = {0: 0, 1: 0, 5: 0, 10: 1, 11: 1, 17: 1}
 NEIGHBOURS = {'fp32': ('bf16x3', 'bf16', 'fp16'), 'bf16x3': ('fp32', 'bf16', 'fp16'), 'bf16': ('fp16', 'bf16x3', 'fp32'),
               'fp16': ('bf16', 'bf16x3', 'fp32')}
 
@@ -61,7 +61,6 @@ ROWS = [
     R('reg-fallback-half-dgrad-s2', 'dgrad', 'half', 'fp32', (2, 64, 16, 16, 64, 3, 2, 1)),
     R('reg-fallback-bf16x3-rowscale', 'fwd', 'bf16x3', 'fp32', (2, 64, 9, 9, 64, 1, 1, 0), rowscale=True, chanscale=True, bias=True),
     # ---- forward: patch kernels ----
-    R('patch8-bf16x3', 'fwd', 'bf16x3', 'bf16x3', (32, 64, 36, 36, 256, 3, 1, 1), knobs={15: 1}, bias=True, slope=0.2),
     R('pers-bf16x3-128', 'fwd', 'bf16x3', 'bf16x3', (2, 64, 23, 21, 128, 3, 1, 1), knobs={0: -2}, bias=True, slope=0.2),
     R('pers-bf16x3-64-residual', 'fwd', 'bf16x3', 'bf16x3', (2, 64, 23, 21, 64, 3, 1, 1), knobs={0: -2}, bias=True, residual=True),
     R('pers-half-prod2', 'fwd', 'half', 'fp16', (2, 64, 23, 21, 128, 3, 1, 1), knobs={0: -2}, bias=True, slope=0.2),
@@ -126,8 +125,6 @@ ROWS = [
     R('rowtap64-split', 'wgrad', 'bf16x3', 'bf16x3', (2, 128, 19, 17, 64, 3, 1, 1), bias=True),
     R('rowtap64-nosplit-half', 'wgrad', 'half', 'bf16', (1, 128, 19, 17, 64, 3, 1, 1), bias=True),
     R('rowtap-tails-off', 'wgrad', 'bf16x3', 'bf16x3', (2, 64, 20, 20, 128, 3, 1, 1), knobs={1: 9}, bias=True),
-    R('rowtap-addr0', 'wgrad', 'bf16x3', 'bf16x3', (2, 64, 20, 20, 128, 3, 1, 1), knobs={8: 0}),
-    R('rowtap-pipe', 'wgrad', 'bf16x3', 'bf16x3', (2, 64, 20, 20, 128, 3, 1, 1), knobs={9: 1}),
     R('rowtap-accumulate-cout320', 'wgrad', 'bf16x3', 'bf16x3', (1, 64, 13, 24, 320, 3, 1, 1), accumulate=True, bias=True),
     R('rowtap-ld192-ndsrgan', 'wgrad_ld', 'half', 'bf16', (2, 128, 17, 19, 64, 3, 1, 1), ldx=192, ldy=192),
     R('wgrad-multi-bf16x3', 'wgrad_multi', 'bf16x3', 'bf16x3', (4, 64, 32, 32, 128, 3, 1, 1)),

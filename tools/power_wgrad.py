@@ -1,4 +1,4 @@
-"""Round 4: board power and shader clock while the RAB weight-gradient pair launch loops (default, per-lane addressing, pipelined),
+"""Round 4: board power and shader clock while the RAB weight-gradient pair launch loops,
 with the persistent fprop kernel beside it for scale.  Energy per launch = mean W x us."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,16 +38,14 @@ def loop(name, fn, flops, setup):
         name, us, wm, sm.get('sclk_mhz_mean') or 0.0, wm * us * 1e-3, wm * us * 1e-6 / flops * 1e12, flops / us / 1e6 / 833.3), flush=True)
 
 
-def cfg(addr, pipe, target):
+def cfg(target):
     def f():
-        lib.srhip_debug_set(8, addr); lib.srhip_debug_set(9, pipe); lib.srhip_debug_set(1, target)
+        lib.srhip_debug_set(1, target)
     return f
 
 
 with ops.conv_math('bf16x3'):
-    loop('fprop 64->256 persistent', lambda: ops.conv2d_fwd_raw(x64[0], w1, b1, 1, 1, 0.2), fl, cfg(1, 0, 0))
-    loop('wgrad pair 64->256 (default: scalar offsets)', lambda: ops.conv2d_wgrad_multi_raw(items), 2 * fl, cfg(1, 0, 0))
-    loop('wgrad pair, per-lane offsets (rounds 1-3)', lambda: ops.conv2d_wgrad_multi_raw(items), 2 * fl, cfg(0, 0, 0))
-    loop('wgrad pair, pipelined, 480 blocks', lambda: ops.conv2d_wgrad_multi_raw(items), 2 * fl, cfg(1, 1, 480))
-    loop('wgrad single 64->256', lambda: ops.conv2d_wgrad_raw(x64[0], t256[0], (256, 64, 3, 3), 1, 1, True), fl, cfg(1, 0, 0))
-cfg(1, 0, 0)()
+    loop('fprop 64->256 persistent', lambda: ops.conv2d_fwd_raw(x64[0], w1, b1, 1, 1, 0.2), fl, cfg(0))
+    loop('wgrad pair 64->256', lambda: ops.conv2d_wgrad_multi_raw(items), 2 * fl, cfg(0))
+    loop('wgrad single 64->256', lambda: ops.conv2d_wgrad_raw(x64[0], t256[0], (256, 64, 3, 3), 1, 1, True), fl, cfg(0))
+cfg(0)()
