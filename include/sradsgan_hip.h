@@ -862,6 +862,40 @@ int srhip_diff_sampler_step(const float* x0, long ldx0, const float* xt, long ld
                             unsigned long long step, void* stream);
 int srhip_diff_quant_u8(const float* x, long ldx, unsigned char* out, long rows, int ch, float lo, float hi, void* stream);
 
+/* ABI 14 (additive) -- backward kernels of the diffusion U-Net and the forward diffusion (csrc/diffusion.hip; model/gdp_train.py).  Same
+ * contract: exact fp32, no atomics, fixed summation orders (re-runs are bit-identical), row strides where noted.
+ *   srhip_diff_gn_stats_offset: byte offset, inside the workspace srhip_diff_gn_fwd was given, of the statistics it leaves there:
+ *     float [n][32][2] = {mean, 1 / sqrt(var + eps)} per (sample, group).  The backward reads them; it does not recompute them.
+ *   srhip_diff_gn_bwd: backward of srhip_diff_gn_fwd from dy [n][p][C] (row stride lddy), x (ldx) and those statistics.  With
+ *     xh = (x - mean) rstd, z = (xh gamma + beta)(1 + scale) + shift, dz = dy silu'(z) (dz = dy when silu == 0), g = dz (1 + scale) gamma:
+ *     dx = rstd (g - mean_grp(g) - xh mean_grp(g xh)) (row stride lddx), dgamma[C], dbeta[C], and, with scale / shift, dscale / dshift
+ *     [n][C] (row stride lddmod; NULL exactly when scale is NULL).  A sample's dx / dscale / dshift read that sample only.  Workspace:
+ *     srhip_diff_gn_bwd_workspace(n, p, C).
+ *   srhip_diff_silu_bwd: dx = dy * sigmoid(x) (1 + x (1 - sigmoid(x))).
+ *   srhip_diff_avgpool2x2_bwd: dx [n][h][w][c] = 0.25 * dy [n][h/2][w/2][c] over each window; odd h or w is an argument error.
+ *   srhip_diff_attn_fwd_lse: srhip_diff_attn_fwd (the same kernel body, `out` bit-identical) that also writes
+ *     lse [n][heads][t] = running maximum + log(running sum) of each query's soft-max row.
+ *   srhip_diff_attn_bwd: dqkv [n][t][heads * 3 * ch] (q | k | v layout of qkv) from dout [n][t][heads * ch], qkv, out and lse, flash
+ *     style on v_mfma_f32_32x32x2_f32: one kernel owns 32 queries per wave (dq, and delta = rowsum(dout * out) into the workspace), one
+ *     owns 32 keys per wave (dk, dv).  No t x t tensor.  Workspace: srhip_diff_attn_bwd_workspace(n, t, heads).
+ *   srhip_diff_q_sample: out = sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * eps over n samples of rows_per_sample rows x ch, every tensor with its
+ *     own row stride; t is int64 [n] ON THE DEVICE, the two schedule arrays are device float [steps] (a t outside [0, steps) is clamped);
+ *     eps = noise, or with noise == NULL srhip_diff_randn(seed, step)'s values over the same [n * rows_per_sample][ch] elements.        */
+size_t srhip_diff_gn_stats_offset(long n, long p);
+size_t srhip_diff_gn_bwd_workspace(long n, long p, int c);
+int srhip_diff_gn_bwd(const float* dy, long lddy, const float* x, long ldx, const float* stats, const float* gamma, const float* beta,
+                      const float* scale, const float* shift, long ldmod, float* dx, long lddx, float* dgamma, float* dbeta, float* dscale,
+                      float* dshift, long lddmod, void* workspace, size_t workspace_bytes, long n, long p, int c, int silu, void* stream);
+int srhip_diff_silu_bwd(const float* dy, const float* x, float* dx, long count, void* stream);
+int srhip_diff_avgpool2x2_bwd(const float* dy, float* dx, int n, int h, int w, int c, void* stream);
+int srhip_diff_attn_fwd_lse(const float* qkv, float* out, float* lse, int n, int t, int heads, int ch, void* stream);
+size_t srhip_diff_attn_bwd_workspace(int n, int t, int heads);
+int srhip_diff_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, void* workspace,
+                        size_t workspace_bytes, int n, int t, int heads, int ch, void* stream);
+int srhip_diff_q_sample(const float* x0, long ldx0, const float* noise, long ldn, float* out, long ldo, const long long* t,
+                        const float* sqrt_ac, const float* sqrt_1mac, int steps, long n, long rows_per_sample, int ch,
+                        unsigned long long seed, unsigned long long step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

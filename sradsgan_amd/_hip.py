@@ -214,6 +214,15 @@ SIGNATURES = {
     'srhip_diff_randn': (_i, [_vp, _l, _l, _i, _u64, _u64, _vp]),
     'srhip_diff_sampler_step': (_i, [_vp, _l] * 4 + [_l, _i, _f, _f, _f, _i, _u64, _u64, _vp]),
     'srhip_diff_quant_u8': (_i, [_vp, _l, _vp, _l, _i, _f, _f, _vp]),
+    'srhip_diff_gn_stats_offset': (_sz, [_l, _l]),
+    'srhip_diff_gn_bwd_workspace': (_sz, [_l, _l, _i]),
+    'srhip_diff_gn_bwd': (_i, [_vp, _l, _vp, _l] + [_vp] * 5 + [_l, _vp, _l] + [_vp] * 4 + [_l, _vp, _sz, _l, _l, _i, _i, _vp]),
+    'srhip_diff_silu_bwd': (_i, [_vp, _vp, _vp, _l, _vp]),
+    'srhip_diff_avgpool2x2_bwd': (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_diff_attn_fwd_lse': (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_diff_attn_bwd_workspace': (_sz, [_i, _i, _i]),
+    'srhip_diff_attn_bwd': (_i, [_vp] * 6 + [_sz] + [_i] * 4 + [_vp]),
+    'srhip_diff_q_sample': (_i, [_vp, _l] * 3 + [_vp] * 3 + [_i, _l, _l, _i, _u64, _u64, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """GDP diffusion super-resolution, sampling only: the reference's `GDP_x0/model/gdp_modules` (unet.py: UNet, diffusion.py:
 GaussianDiffusion) and `networks.define_G`, run from a trained `I*_E*_gen.pth` on the HIP kernels.  There is no backward pass, no
-training step and no optimiser here.
+training step and no optimiser here: the classes below keep their parameters frozen and refuse to train.  model/gdp_train.py derives
+the trainable ones from them (TrainableUNet, TrainableDiffusion, DDPM).
 
   UNet               guided-diffusion's U-Net with the reference's signature, defaults and state-dict keys.  Activations are NHWC;
                      every conv (3x3, and the 1x1 skip / qkv / proj_out) goes through srhip_conv2d_fwd with its bias and residual
@@ -28,7 +29,7 @@ GROUPS = 32
 SCHEDULE_BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
                     'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_variance',
                     'posterior_log_variance_clipped', 'posterior_mean_coef1', 'posterior_mean_coef2')
-_TRAINING = 'training is not built: this is the sampler'
+_TRAINING = 'training is not built: this is the sampler (gdp_train.TrainableDiffusion and gdp_train.DDPM train)'
 
 
 def _p(t):
