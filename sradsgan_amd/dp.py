@@ -57,6 +57,15 @@ class ParamArena:
     def zero_grad(self):
         self.flat_g.zero_()
 
+    def adam_step(self, lr, b1, b2, eps, grad_scale=1.0, clip=0.0):
+        """One fused Adam step over the arena (srhip_adam_step: gradients x grad_scale, parameters clamped to +-clip when clip > 0) on
+        the current stream.  It writes through raw pointers: the caller follows it with ops.bump_weight_epoch()."""
+        from . import _hip
+        from .ops import _p, _stream
+        _hip.check(_hip.lib().srhip_adam_step(_p(self.flat_p), _p(self.flat_g), _p(self.exp_avg), _p(self.exp_avg_sq), _p(self.step_state),
+                                              self.numel, float(lr), float(b1), float(b2), float(eps), float(grad_scale), float(clip),
+                                              _stream()), 'adam_step')
+
     def check_views(self):
         """True while every parameter and gradient still aliases the arena (module.to()/zero_grad(
         set_to_none=True) would silently break that)."""

@@ -14,144 +14,22 @@ the trainable ones from them (TrainableUNet, TrainableDiffusion, DDPM)
   define_G / load_gen / gdp_super_resolve   the reference's config dict -> model, its checkpoint -> weights, and sr_mfe.py's
                      validation path (uint8 LR -> bicubic -> [-1, 1] -> sampler -> tensor2img) without files in between.
 
-ctypes calls are made here, as classify.py and scene.py do."""
-import ctypes
+The kernels of csrc/diffusion.hip are called through model/gdp_kernels.py.  The U-Net's forward is written once, over ops and those
+differentiable kernels: it runs under torch.no_grad() here and with grad enabled in gdp_train.TrainableUNet."""
 import math
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _hip, data as sdata, ops
+from .. import data as sdata, ops
+from .gdp_kernels import (GROUPS, avg_pool2x2, group_norm_act, qkv_attention, quantize_u8, randn_rows, sampler_step,  # noqa: F401
+                          silu)
 
-CL = torch.channels_last
-GROUPS = 32
 SCHEDULE_BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
                     'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_variance',
                     'posterior_log_variance_clipped', 'posterior_mean_coef1', 'posterior_mean_coef2')
 _TRAINING = 'training is not built: this is the sampler (gdp_train.TrainableDiffusion and gdp_train.DDPM train)'
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ops._stream()
-
-
-def _rows(t, what):
-    """(t, row stride) of a float32 device tensor [..., rows, C] whose channels are adjacent and whose rows lie `ld >= C` apart (a channel
-    slice of a wider row buffer, or a dense one)."""
-    ops._require_gpu(t, what)
-    if t.dim() < 2 or t.stride(-1) != 1:
-        raise ValueError('%s: channels must be the innermost, adjacent dimension, got strides %s' % (what, t.stride()))
-    ld = t.stride(-2) if t.shape[-2] > 1 else max(t.stride(-2), t.shape[-1])
-    step = ld
-    for d in range(t.dim() - 2, -1, -1):
-        if t.shape[d] > 1 and t.stride(d) != step:
-            raise ValueError('%s: rows must lie one row stride apart, got shape %s strides %s' % (what, tuple(t.shape), t.stride()))
-        step *= t.shape[d]
-    if ld < t.shape[-1]:
-        raise ValueError('%s: row stride %d < %d channels' % (what, ld, t.shape[-1]))
-    return t, ld
-
-
-# ------------------------------------------------------------------------------------------------------------------------------ #
-# kernels (csrc/diffusion.hip)
-# ------------------------------------------------------------------------------------------------------------------------------ #
-def group_norm_act(x, weight, bias, scale=None, shift=None, silu=False, eps=1e-5):
-    """nn.GroupNorm(32, C) over x [n, p, C] (rows may be a channel slice: row stride >= C), then y * (1 + scale) + shift with scale /
-    shift [n, C] (both or neither), then SiLU if asked.  Returns a dense [n, p, C] tensor."""
-    x, ldx = _rows(x, 'group_norm_act')
-    if x.dim() != 3:
-        raise ValueError('group_norm_act: x must be [n, p, C], got %s' % (tuple(x.shape),))
-    n, p, c = x.shape
-    y = torch.empty(n, p, c, device=x.device, dtype=torch.float32)
-    ldy = c
-    ldmod = 0
-    if scale is not None:
-        scale, ldmod = _rows(scale, 'group_norm_act')
-        shift, lds = _rows(shift, 'group_norm_act')
-        if lds != ldmod or tuple(scale.shape) != (n, c) or tuple(shift.shape) != (n, c):
-            raise ValueError('group_norm_act: scale and shift must be [n, C] with one row stride')
-    lib = _hip.lib()
-    nbytes = lib.srhip_diff_gn_workspace(n, p)
-    ws = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
-    _hip.check(lib.srhip_diff_gn_fwd(_p(x), ldx, _p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(scale), _p(shift),
-                                     ldmod, _p(y), ldy, _p(ws), ws.numel() * 4, n, p, c, float(eps), int(bool(silu)), _stream()),
-               'diff_gn_fwd')
-    return y
-
-
-def silu(x):
-    ops._require_gpu(x, 'silu')
-    x = x.contiguous()
-    y = torch.empty_like(x)
-    _hip.check(_hip.lib().srhip_diff_silu_fwd(_p(x), _p(y), x.numel(), _stream()), 'diff_silu_fwd')
-    return y
-
-
-def avg_pool2x2(x):
-    """nn.AvgPool2d(2) of a logical [n, C, h, w] tensor (NHWC memory); h and w must be even."""
-    ops._require_gpu(x, 'avg_pool2x2')
-    x = ops.nhwc(x)
-    n, c, h, w = x.shape
-    y = ops.empty_nhwc(n, c, h // 2, w // 2, x)
-    _hip.check(_hip.lib().srhip_diff_avgpool2x2_fwd(_p(x), _p(y), n, h, w, c, _stream()), 'diff_avgpool2x2_fwd')
-    return y
-
-
-def qkv_attention(qkv, heads):
-    """QKVAttentionLegacy on the qkv rows [n, t, heads * 3 * ch] (each head's q | k | v adjacent), ch in {32, 64} -> [n, t, heads * ch]."""
-    ops._require_gpu(qkv, 'qkv_attention')
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads):
-        raise ValueError('qkv_attention: expected [n, t, heads * 3 * ch], got %s for %d heads' % (tuple(qkv.shape), heads))
-    qkv = qkv.contiguous()
-    n, t, width = qkv.shape
-    ch = width // (3 * heads)
-    out = torch.empty(n, t, heads * ch, device=qkv.device, dtype=torch.float32)
-    _hip.check(_hip.lib().srhip_diff_attn_fwd(_p(qkv), _p(out), n, t, heads, ch, _stream()), 'diff_attn_fwd')
-    return out
-
-
-def randn_rows(out, seed, step):
-    """Fill out [..., rows, C] (row stride >= C) with the Philox normals of (seed, step); element index = row * C + channel."""
-    out, ld = _rows(out, 'randn_rows')
-    rows = out.numel() // out.shape[-1]
-    _hip.check(_hip.lib().srhip_diff_randn(_p(out), ld, rows, out.shape[-1], int(seed), int(step), _stream()), 'diff_randn')
-    return out
-
-
-def sampler_step(x0, xt, out, c1, c2, logvar, t_nonzero, noise=None, seed=0, step=0):
-    """out = c1 * clamp(x0, -1, 1) + c2 * xt + (t_nonzero ? exp(0.5 * logvar) * noise : 0) over rows [..., rows, C], every tensor with its
-    own row stride; out may be xt.  noise=None draws randn_rows(seed, step)'s values in the kernel."""
-    x0, l0 = _rows(x0, 'sampler_step')
-    xt, lt = _rows(xt, 'sampler_step')
-    out, lo = _rows(out, 'sampler_step')
-    ln = 0
-    if noise is not None:
-        noise, ln = _rows(noise, 'sampler_step')
-    ch = x0.shape[-1]
-    rows = x0.numel() // ch
-    for t in (xt, out) + ((noise,) if noise is not None else ()):
-        if tuple(t.shape) != tuple(x0.shape):
-            raise ValueError('sampler_step: shapes differ: %s vs %s' % (tuple(t.shape), tuple(x0.shape)))
-    _hip.check(_hip.lib().srhip_diff_sampler_step(_p(x0), l0, _p(xt), lt, _p(noise), ln, _p(out), lo, rows, ch, float(c1), float(c2),
-                                                  float(logvar), int(bool(t_nonzero)), int(seed), int(step), _stream()),
-               'diff_sampler_step')
-    return out
-
-
-def quantize_u8(x, min_max=(-1.0, 1.0)):
-    """core/metrics.py tensor2img on the device: x [..., rows, C] float32 -> uint8 of the same shape, clamp to min_max, map to [0, 1],
-    x 255, round half to even."""
-    x, ld = _rows(x, 'quantize_u8')
-    out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    rows = x.numel() // x.shape[-1]
-    _hip.check(_hip.lib().srhip_diff_quant_u8(_p(x), ld, _p(out), rows, x.shape[-1], float(min_max[0]), float(min_max[1]), _stream()),
-               'diff_quant_u8')
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ #
@@ -175,13 +53,15 @@ def _image(rows, h, w):
 
 
 def _conv(x, conv, residual=None):
-    k = conv.weight.shape[2] if conv.weight.dim() == 4 else 1
-    return ops.conv2d_fwd_raw(x, conv.weight, conv.bias, 1, k // 2, residual=residual)
+    w = conv.weight
+    if w.dim() == 4:
+        return ops.conv2d(x, w, conv.bias, 1, w.shape[2] // 2, None, residual)
+    return ops.linear(x, w, conv.bias, residual)             # nn.Linear and the attention's nn.Conv1d(k = 1): the 1 x 1 conv route
 
 
-def _norm(x, gn, scale=None, shift=None, act=False):
+def _norm(x, gn, mod=None, act=False):
     n, c, h, w = x.shape
-    return _image(group_norm_act(_tokens(x), gn.weight, gn.bias, scale, shift, act, gn.eps), h, w)
+    return _image(group_norm_act(_tokens(x), gn.weight, gn.bias, silu=act, eps=gn.eps, mod=mod), h, w)
 
 
 class _Resample(nn.Module):
@@ -217,11 +97,10 @@ class ResBlock(nn.Module):
         """emb_act: SiLU(emb) as [n, E, 1, 1] (the SiLU of emb_layers is the same for every block: taken once per forward)."""
         h = _norm(x, self.in_layers[0], act=True)
         if self.updown:
-            h, x = self.h_upd(h), self.x_upd(x)
+            h, x = self.h_upd.forward(h), self.x_upd.forward(x)
         h = _conv(h, self.in_layers[2])
-        lin = self.emb_layers[1]
-        mod = ops.conv2d_fwd_raw(emb_act, lin.weight, lin.bias, 1, 0).reshape(x.shape[0], 2 * self.out_channel)
-        h = _norm(h, self.out_layers[0], mod[:, :self.out_channel], mod[:, self.out_channel:], act=True)
+        mod = _conv(emb_act, self.emb_layers[1]).reshape(x.shape[0], 2 * self.out_channel)      # scale | shift, as the kernel reads it
+        h = _norm(h, self.out_layers[0], mod, act=True)
         skip = x if isinstance(self.skip_connection, nn.Identity) else _conv(x, self.skip_connection)
         return _conv(h, self.out_layers[3], residual=skip)
 
@@ -251,11 +130,17 @@ class AttentionBlock(nn.Module):
 
 
 class _Block(nn.Sequential):
-    """TimestepEmbedSequential"""
+    """TimestepEmbedSequential.  The walk invokes the holders' `forward` directly (here, in ResBlock and in UNet._walk): they carry no
+    hooks, and nn.Module's call machinery on some 75 of them per forward measured 0.3 % of a fp32 training step."""
 
     def forward(self, x, emb_act):
         for layer in self:
-            x = layer(x, emb_act) if isinstance(layer, ResBlock) else (layer(x) if isinstance(layer, AttentionBlock) else _conv(x, layer))
+            if isinstance(layer, ResBlock):
+                x = layer.forward(x, emb_act)
+            elif isinstance(layer, AttentionBlock):
+                x = layer.forward(x)
+            else:
+                x = _conv(x, layer)
         return x
 
 
@@ -354,40 +239,44 @@ class UNet(nn.Module):
     def embed(self, emb_in):
         """time_embed on sinusoid rows [n, model_channels] (device) -> SiLU(emb) as [n, 4 * model_channels, 1, 1]: every ResBlock's
         emb_layers starts with that SiLU."""
-        n = emb_in.shape[0]
-        l0, l2 = self.time_embed[0], self.time_embed[2]
-        e = ops.conv2d_fwd_raw(emb_in.reshape(n, -1, 1, 1), l0.weight, l0.bias, 1, 0)
-        e = ops.conv2d_fwd_raw(silu(e), l2.weight, l2.bias, 1, 0)
-        return silu(e)
+        e = _conv(emb_in.reshape(emb_in.shape[0], -1, 1, 1), self.time_embed[0])
+        return silu(_conv(silu(e), self.time_embed[2]))
+
+    def _walk(self, x, emb_in):
+        """The forward on x [N, in_channel, H, W] (NHWC memory) and sinusoid rows, in the caller's grad mode and conv arithmetic."""
+        emb_act = self.embed(emb_in)
+        h, hs = x, []
+        for block in self.input_blocks:
+            h = block.forward(h, emb_act)
+            hs.append(h)
+        h = self.middle_block.forward(h, emb_act)
+        for block in self.output_blocks:
+            h = block.forward(ops.cat_channels([h, hs.pop()]), emb_act)
+        return _conv(_norm(h, self.out[0], act=True), self.out[2])
+
+    def _checked_rows(self, who, x, timesteps, y):
+        """UNet.forward's input checks, with `who` in the messages -> the sinusoid rows of `timesteps` on x's device."""
+        if y is not None:
+            raise NotImplementedError('num_classes: class conditioning is not built')
+        ops._require_gpu(x, who)
+        if x.dim() != 4 or x.shape[1] != self.in_channel:
+            raise ValueError('%s: input must be [N, %d, H, W], got %s' % (who, self.in_channel, tuple(x.shape)))
+        down = 2 ** (len(self.channel_mults) - 1)
+        if x.shape[2] % down or x.shape[3] % down:
+            raise ValueError('%s: H and W must be multiples of %d, got %d x %d' % (who, down, x.shape[2], x.shape[3]))
+        return timestep_embedding(torch.as_tensor(timesteps), self.model_channels).to(x.device)
 
     @torch.no_grad()
     def forward_embedded(self, x, emb_in):
         if ops.get_conv_math() == 'half':                # inference must not move with the training arithmetic
             with ops.conv_math('bf16x3'):
-                return self.forward_embedded(x, emb_in)
-        emb_act = self.embed(emb_in)
-        h, hs = x, []
-        for block in self.input_blocks:
-            h = block(h, emb_act)
-            hs.append(h)
-        h = self.middle_block(h, emb_act)
-        for block in self.output_blocks:
-            h = block(ops.cat_channels([h, hs.pop()]), emb_act)
-        return _conv(_norm(h, self.out[0], act=True), self.out[2])
+                return self._walk(x, emb_in)
+        return self._walk(x, emb_in)
 
     @torch.no_grad()
     def forward(self, x, timesteps, y=None):
         """x [N, in_channel, H, W] float32 on the device, timesteps [N] -> [N, out_channel, H, W] (NHWC memory).  Eval mode, no grad."""
-        if y is not None:
-            raise NotImplementedError('num_classes: class conditioning is not built')
-        ops._require_gpu(x, 'gdp.UNet')
-        if x.dim() != 4 or x.shape[1] != self.in_channel:
-            raise ValueError('gdp.UNet: input must be [N, %d, H, W], got %s' % (self.in_channel, tuple(x.shape)))
-        down = 2 ** (len(self.channel_mults) - 1)
-        if x.shape[2] % down or x.shape[3] % down:
-            raise ValueError('gdp.UNet: H and W must be multiples of %d, got %d x %d' % (down, x.shape[2], x.shape[3]))
-        emb_in = timestep_embedding(torch.as_tensor(timesteps), self.model_channels).to(x.device)
-        return self.forward_embedded(ops.nhwc(x), emb_in)
+        return self.forward_embedded(ops.nhwc(x), self._checked_rows('gdp.UNet', x, timesteps, y))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ #
@@ -420,6 +309,11 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
         alphas = alphas / alphas[0]
         return (1 - alphas[1:] / alphas[:-1]).clamp(max=0.999).numpy()
     raise NotImplementedError(schedule)
+
+
+def draw_seed():
+    """A Philox seed from torch's CPU generator (a host tensor: no device sync), for callers that pass neither noise nor seed."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
 class GaussianDiffusion(nn.Module):
@@ -470,11 +364,14 @@ class GaussianDiffusion(nn.Module):
         self._logvar = self.posterior_log_variance_clipped.detach().cpu().tolist()
         self._sinusoid = None
 
-    def _emb_rows(self, i, b, device):
+    def _table(self, device):
+        """Sinusoid rows of every timestep, [T, model_channels] on the device: the sampler reads row i, a training step gathers by t."""
         if self._sinusoid is None or self._sinusoid.device != device:
-            mc = self.denoise_fn.model_channels
-            self._sinusoid = timestep_embedding(torch.arange(self.num_timesteps), mc).to(device)
-        return self._sinusoid[i:i + 1].expand(b, -1).contiguous()
+            self._sinusoid = timestep_embedding(torch.arange(self.num_timesteps), self.denoise_fn.model_channels).to(device)
+        return self._sinusoid
+
+    def _emb_rows(self, i, b, device):
+        return self._table(device)[i:i + 1].expand(b, -1).contiguous()
 
     def _need_schedule(self):
         if self.num_timesteps is None:
@@ -500,7 +397,7 @@ class GaussianDiffusion(nn.Module):
         if condition_x is not None:
             buf[..., c:] = condition_x.permute(0, 2, 3, 1)
         if noise is None and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = draw_seed()
         self._step(buf, c, i, None if noise is None else noise.permute(0, 2, 3, 1).contiguous(), seed or 0, step)
         return buf[..., :c].permute(0, 3, 1, 2)
 
@@ -522,7 +419,7 @@ class GaussianDiffusion(nn.Module):
             ops._require_gpu(noise, 'gdp sampler (noise)')
             noise = noise.permute(0, 1, 3, 4, 2).contiguous()
         elif seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = draw_seed()
         extra = cond.shape[1] if cond is not None else 0
         buf = torch.empty(b, h, w, c + extra, device=device, dtype=torch.float32)
         if cond is not None:
@@ -574,18 +471,22 @@ class GaussianDiffusion(nn.Module):
         raise NotImplementedError('interpolate is not built')
 
 
-def define_G(opt):
-    """The reference's networks.define_G for which_model_G = 'gdp': only the arguments it passes reach the U-Net, everything else
-    (128 base channels, heads of 64, attention at 8x down-sampling) is UNet's default."""
+def build_G(opt, unet, diffusion):
+    """The reference's networks.define_G for which_model_G = 'gdp', over the classes `unet` and `diffusion`: only the arguments it
+    passes reach the U-Net, everything else (128 base channels, heads of 64, attention at 8x down-sampling) is UNet's default."""
     m = opt['model']
     if m['which_model_G'] != 'gdp':
         raise NotImplementedError("which_model_G=%r: only 'gdp' is built (the reference ships no ddpm module)" % m['which_model_G'])
     u = m['unet']
-    model = UNet(in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u.get('norm_groups') or 32,
+    model = unet(in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u.get('norm_groups') or 32,
                  inner_channel=u['inner_channel'], channel_mults=u['channel_multiplier'], attn_res=u['attn_res'],
                  res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=m['diffusion']['image_size'])
-    return GaussianDiffusion(model, image_size=m['diffusion']['image_size'], channels=m['diffusion']['channels'], loss_type='l2',
-                             conditional=m['diffusion']['conditional'], schedule_opt=m['beta_schedule']['train'])
+    return diffusion(model, image_size=m['diffusion']['image_size'], channels=m['diffusion']['channels'], loss_type='l2',
+                     conditional=m['diffusion']['conditional'], schedule_opt=m['beta_schedule']['train'])
+
+
+def define_G(opt):
+    return build_G(opt, UNet, GaussianDiffusion)
 
 
 def load_gen(netG, path):

@@ -3,15 +3,13 @@
 parameters frozen and refuse to train; the classes here derive from them, share their module tree and state-dict keys, and add the
 backward pass.
 
-  group_norm_act / silu / avg_pool2x2 / qkv_attention   autograd Functions over csrc/diffusion.hip: the forward kernels of gdp.py (the
-                     attention one in its lse-emitting form, same bits) and srhip_diff_*_bwd.  Exact fp32, no atomics.
-  TrainableUNet      gdp.UNet with parameters that require grad.  With grad enabled the forward runs the same kernels through
-                     ops.conv2d / ops.linear (residual epilogues for the skip adds), ops.cat_channels and ops.upsample_nearest, so its
-                     output has the bits of gdp.UNet.forward_embedded; without grad it IS that forward.  Conv arithmetic `half` is
+  TrainableUNet      gdp.UNet with parameters that require grad.  With grad enabled it runs gdp.UNet's one walk (ops.conv2d /
+                     ops.linear, ops.cat_channels, ops.upsample_nearest and the differentiable kernels of model/gdp_kernels.py), so
+                     its output has the bits of gdp.UNet.forward_embedded; without grad it IS that forward.  Conv arithmetic `half` is
                      replaced by `bf16x3` for forward and backward alike (_HoldConvMath).
   TrainableDiffusion set_loss, q_sample (srhip_diff_q_sample writes x_t into channels 0..2 of the U-Net input, gathering the schedule
                      coefficients by the device tensor t) and p_losses (sum-reduced, as the reference's reduction='sum').
-  DDPM               the reference's model surface: feed_data, optimize_parameters (dp.ParamArena + srhip_adam_step, no host sync in
+  DDPM               the reference's model surface: feed_data, optimize_parameters (dp.ParamArena.adam_step, no host sync in
                      the step), test / sample, save_network / load_network in the reference's file layout.
   training_batch     uint8 HR tiles -> {'HR', 'SR', 'LR'} as prepare_data.py + LRHR_dataset.py make them.
 
@@ -22,284 +20,23 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 from torch.autograd import Function
-from torch.autograd.function import once_differentiable
 
-from .. import _hip, data as sdata, dp, ops
+from .. import data as sdata, dp, ops
 from . import gdp
-from .gdp import _image, _p, _rows, _stream, _tokens
+from .gdp_kernels import (attention_bwd_raw, attention_fwd_lse, avg_pool2x2, avg_pool2x2_bwd, group_norm_act,  # noqa: F401
+                          group_norm_bwd_raw, group_norm_fwd_raw, q_sample_rows, qkv_attention, silu)
 
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ #
-# differentiable kernels (csrc/diffusion.hip)
+# the U-Net with a backward pass: gdp.UNet's walk, run with grad enabled
 # ------------------------------------------------------------------------------------------------------------------------------ #
-def group_norm_fwd_raw(x, weight, bias, mod, silu, eps=1e-5):
-    """(y dense [n, p, C], statistics [n, 32, 2] = mean | 1 / sigma as the forward kernel leaves them in its workspace) of x [n, p, C]
-    (row stride >= C) with mod [n, 2 C] = scale | shift or None."""
-    x, ldx = _rows(x, 'group_norm_act')
-    if x.dim() != 3:
-        raise ValueError('group_norm_act: x must be [n, p, C], got %s' % (tuple(x.shape),))
-    n, p, c = x.shape
-    scale = shift = None
-    if mod is not None:
-        if tuple(mod.shape) != (n, 2 * c) or not mod.is_contiguous():
-            raise ValueError('group_norm_act: scale | shift must be a dense [n, 2 C] = %s, got %s' % ((n, 2 * c), tuple(mod.shape)))
-        scale, shift = mod[:, :c], mod[:, c:]
-    y = torch.empty(n, p, c, device=x.device, dtype=torch.float32)
-    lib = _hip.lib()
-    ws = torch.empty(max(1, lib.srhip_diff_gn_workspace(n, p) // 4), device=x.device, dtype=torch.float32)
-    _hip.check(lib.srhip_diff_gn_fwd(_p(x), ldx, _p(weight), _p(bias), _p(scale), _p(shift), 2 * c, _p(y), c, _p(ws), ws.numel() * 4,
-                                     n, p, c, float(eps), int(bool(silu)), _stream()), 'diff_gn_fwd')
-    off = lib.srhip_diff_gn_stats_offset(n, p) // 4
-    return y, ws[off:off + n * gdp.GROUPS * 2].view(n, gdp.GROUPS, 2)
-
-
-def group_norm_bwd_raw(dy, x, stats, weight, bias, mod, silu, out=None):
-    """(dx [n, p, C], dgamma, dbeta, dmod [n, 2 C] or None) from dy [n, p, C] and the forward's x and statistics.  dy may be a channel
-    slice of a wider row buffer (any other layout is copied dense); dx is dense, or `out` ([n, p, C], row stride >= C)."""
-    x, ldx = _rows(x, 'group_norm_act backward')
-    n, p, c = x.shape
-    try:
-        dy, lddy = _rows(dy, 'group_norm_act backward')
-    except ValueError:                                   # e.g. an NCHW-dense gradient seen through the token view
-        dy, lddy = dy.contiguous(), c
-    if tuple(dy.shape) != (n, p, c):
-        raise ValueError('group_norm_act backward: dy %s does not match x %s' % (tuple(dy.shape), (n, p, c)))
-    if out is None:
-        dx, lddx = torch.empty(n, p, c, device=x.device, dtype=torch.float32), c
-    else:
-        dx, lddx = _rows(out, 'group_norm_act backward')
-        if tuple(dx.shape) != (n, p, c):
-            raise ValueError('group_norm_act backward: out %s does not match x %s' % (tuple(dx.shape), (n, p, c)))
-    dgamma, dbeta = torch.empty_like(weight), torch.empty_like(bias)
-    scale = shift = dmod = dscale = dshift = None
-    if mod is not None:
-        scale, shift = mod[:, :c], mod[:, c:]
-        dmod = torch.empty_like(mod)
-        dscale, dshift = dmod[:, :c], dmod[:, c:]
-    lib = _hip.lib()
-    ws = torch.empty(max(1, lib.srhip_diff_gn_bwd_workspace(n, p, c) // 4), device=x.device, dtype=torch.float32)
-    _hip.check(lib.srhip_diff_gn_bwd(_p(dy), lddy, _p(x), ldx, _p(stats), _p(weight), _p(bias), _p(scale), _p(shift), 2 * c, _p(dx), lddx,
-                                     _p(dgamma), _p(dbeta), _p(dscale), _p(dshift), 2 * c, _p(ws), ws.numel() * 4, n, p, c,
-                                     int(bool(silu)), _stream()), 'diff_gn_bwd')
-    return dx, dgamma, dbeta, dmod
-
-
-class _GroupNormAct(Function):
-    """x [n, p, C] (row stride >= C), mod [n, 2 C] = scale | shift or None -> dense [n, p, C]."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, mod, silu, eps):
-        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
-        mod = mod.contiguous() if mod is not None else None
-        y, stats = group_norm_fwd_raw(x, weight, bias, mod, silu, eps)
-        ctx.save_for_backward(x, weight, bias, mod, stats)
-        ctx.silu = bool(silu)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        x, weight, bias, mod, stats = ctx.saved_tensors
-        return group_norm_bwd_raw(dy, x, stats, weight, bias, mod, ctx.silu) + (None, None)
-
-
-def group_norm_act(x, weight, bias, scale=None, shift=None, silu=False, eps=1e-5, mod=None):
-    """gdp.group_norm_act, differentiable in x, weight, bias and the modulation.  The modulation is `mod` [n, 2 C] = scale | shift (the
-    emb_layers row as it stands) or `scale` and `shift` [n, C]."""
-    if (scale is None) != (shift is None):
-        raise ValueError('group_norm_act: scale and shift come together')
-    if scale is not None:
-        mod = torch.cat([scale, shift], dim=1)
-    return _GroupNormAct.apply(x, weight, bias, mod, silu, eps)
-
-
-class _SiLU(Function):
-    @staticmethod
-    def forward(ctx, x):
-        ops._require_gpu(x, 'silu')
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        _hip.check(_hip.lib().srhip_diff_silu_fwd(_p(x), _p(y), x.numel(), _stream()), 'diff_silu_fwd')
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        x, = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        _hip.check(_hip.lib().srhip_diff_silu_bwd(_p(dy), _p(x), _p(dx), x.numel(), _stream()), 'diff_silu_bwd')
-        return dx
-
-
-def silu(x):
-    return _SiLU.apply(x)
-
-
-class _AvgPool2x2(Function):
-    @staticmethod
-    def forward(ctx, x):
-        ops._require_gpu(x, 'avg_pool2x2')
-        x = ops.nhwc(x)
-        n, c, h, w = x.shape
-        y = ops.empty_nhwc(n, c, h // 2, w // 2, x)
-        _hip.check(_hip.lib().srhip_diff_avgpool2x2_fwd(_p(x), _p(y), n, h, w, c, _stream()), 'diff_avgpool2x2_fwd')
-        ctx.shape = (n, c, h, w)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        return avg_pool2x2_bwd(dy, ctx.shape)
-
-
-def avg_pool2x2(x):
-    return _AvgPool2x2.apply(x)
-
-
-def avg_pool2x2_bwd(dy, shape):
-    """The pool's backward alone: dy [n, C, h / 2, w / 2] -> dx of `shape` = [n, C, h, w] (NHWC memory)."""
-    ops._require_gpu(dy, 'avg_pool2x2_bwd')
-    n, c, h, w = shape
-    dy = ops.nhwc(dy)
-    if tuple(dy.shape) != (n, c, h // 2, w // 2):
-        raise ValueError('avg_pool2x2_bwd: dy %s does not belong to an input of %s' % (tuple(dy.shape), tuple(shape)))
-    dx = ops.empty_nhwc(n, c, h, w, dy)
-    _hip.check(_hip.lib().srhip_diff_avgpool2x2_bwd(_p(dy), _p(dx), n, h, w, c, _stream()), 'diff_avgpool2x2_bwd')
-    return dx
-
-
-def attention_fwd_lse(qkv, heads):
-    """(out [n, t, heads * ch], lse [n, heads, t]) of gdp.qkv_attention's arithmetic; `out` has its bits."""
-    ops._require_gpu(qkv, 'qkv_attention')
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads):
-        raise ValueError('qkv_attention: expected [n, t, heads * 3 * ch], got %s for %d heads' % (tuple(qkv.shape), heads))
-    qkv = qkv.contiguous()
-    n, t, width = qkv.shape
-    ch = width // (3 * heads)
-    out = torch.empty(n, t, heads * ch, device=qkv.device, dtype=torch.float32)
-    lse = torch.empty(n, heads, t, device=qkv.device, dtype=torch.float32)
-    _hip.check(_hip.lib().srhip_diff_attn_fwd_lse(_p(qkv), _p(out), _p(lse), n, t, heads, ch, _stream()), 'diff_attn_fwd_lse')
-    return qkv, out, lse
-
-
-def attention_bwd_raw(qkv, out, lse, dout, heads):
-    """dqkv [n, t, heads * 3 * ch] from what attention_fwd_lse returned and dout [n, t, heads * ch]."""
-    n, t, width = qkv.shape
-    dout = dout.contiguous()
-    if dout.data_ptr() % 16:
-        dout = dout.clone()
-    dqkv = torch.empty_like(qkv)
-    lib = _hip.lib()
-    ws = torch.empty(max(1, lib.srhip_diff_attn_bwd_workspace(n, t, heads) // 4), device=qkv.device, dtype=torch.float32)
-    _hip.check(lib.srhip_diff_attn_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel() * 4, n, t, heads,
-                                       width // (3 * heads), _stream()), 'diff_attn_bwd')
-    return dqkv
-
-
-class _QKVAttention(Function):
-    @staticmethod
-    def forward(ctx, qkv, heads):
-        qkv, out, lse = attention_fwd_lse(qkv, heads)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.heads = heads
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        return attention_bwd_raw(qkv, out, lse, dout, ctx.heads), None
-
-
-def qkv_attention(qkv, heads):
-    return _QKVAttention.apply(qkv, heads)
-
-
-def q_sample_rows(x0, t, sqrt_ac, sqrt_1mac, out, noise=None, seed=0, step=0):
-    """out = sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * eps over rows [B, ..., C] (each tensor with its own row stride; `out` may be a channel
-    slice of the U-Net input).  t: int64 [B] on the device.  eps = noise, or gdp.randn_rows(seed, step)'s draws taken in the kernel."""
-    x0, l0 = _rows(x0, 'q_sample')
-    out, lo = _rows(out, 'q_sample')
-    ln = 0
-    if noise is not None:
-        noise, ln = _rows(noise, 'q_sample')
-    for other in (out,) + ((noise,) if noise is not None else ()):
-        if tuple(other.shape) != tuple(x0.shape):
-            raise ValueError('q_sample: shapes differ: %s vs %s' % (tuple(other.shape), tuple(x0.shape)))
-    b, ch = x0.shape[0], x0.shape[-1]
-    if not t.is_cuda or t.dtype != torch.int64 or tuple(t.shape) != (b,):
-        raise TypeError('q_sample: t must be an int64 device tensor of shape (%d,), got %s %s on %s' % (b, t.dtype, tuple(t.shape), t.device))
-    t = t.contiguous()
-    _hip.check(_hip.lib().srhip_diff_q_sample(_p(x0), l0, _p(noise), ln, _p(out), lo, _p(t), _p(sqrt_ac), _p(sqrt_1mac), sqrt_ac.numel(), b,
-                                              x0.numel() // (b * ch), ch, int(seed), int(step), _stream()), 'diff_q_sample')
-    return out
-
-
-# ------------------------------------------------------------------------------------------------------------------------------ #
-# the U-Net with a backward pass: gdp.py's modules, walked with differentiable ops
-# ------------------------------------------------------------------------------------------------------------------------------ #
-def _conv(x, conv, residual=None):
-    w = conv.weight
-    if w.dim() == 4:
-        return ops.conv2d(x, w, conv.bias, 1, w.shape[2] // 2, None, residual)
-    return ops.linear(x, w, conv.bias, residual)             # nn.Linear and the attention's nn.Conv1d(k = 1): the 1 x 1 conv route
-
-
-def _norm(x, gn, mod=None, act=False):
-    n, c, h, w = x.shape
-    return _image(_GroupNormAct.apply(_tokens(x), gn.weight, gn.bias, mod, act, gn.eps), h, w)
-
-
-def _res_forward(blk, x, emb_act):
-    h = _norm(x, blk.in_layers[0], act=True)
-    if blk.updown:
-        if blk.h_upd.up:
-            h, x = ops.upsample_nearest(h, 2), ops.upsample_nearest(x, 2)
-        else:
-            h, x = avg_pool2x2(h), avg_pool2x2(x)
-    h = _conv(h, blk.in_layers[2])
-    mod = _conv(emb_act, blk.emb_layers[1]).reshape(x.shape[0], 2 * blk.out_channel)
-    h = _norm(h, blk.out_layers[0], mod, act=True)
-    skip = x if isinstance(blk.skip_connection, nn.Identity) else _conv(x, blk.skip_connection)
-    return _conv(h, blk.out_layers[3], residual=skip)
-
-
-def _attn_forward(blk, x):
-    n, c, h, w = x.shape
-    qkv = _conv(_norm(x, blk.norm), blk.qkv)
-    a = qkv_attention(_tokens(qkv), blk.num_heads)
-    return _conv(_image(a, h, w), blk.proj_out, residual=x)
-
-
-def _block_forward(block, x, emb_act):
-    for layer in block:
-        if isinstance(layer, gdp.ResBlock):
-            x = _res_forward(layer, x, emb_act)
-        elif isinstance(layer, gdp.AttentionBlock):
-            x = _attn_forward(layer, x)
-        else:
-            x = _conv(x, layer)
-    return x
-
-
 def _thaw(net):
-    """Parameters require grad and join the per-step batched re-pack: the static mark goes, and packed images made while the net was
-    frozen (a net that was sampled from first) are dropped, so that the next use packs them again and registers them."""
-    dropped = set()
+    """Parameters require grad and join the per-step batched re-pack (ops.mark_trainable)."""
     for p in net.parameters():
         p.requires_grad_(True)
-        dropped.update(id(ent) for ent in getattr(p, '_srhip_packed', {}).values())
-        for attr in ('_srhip_static', '_srhip_packed'):
-            if hasattr(p, attr):
-                delattr(p, attr)
-    reg = ops._registry                                  # a net that has trained before: its images leave the batched re-pack too
-    if any(id(ent) in dropped for ent in reg.entries):
-        reg.entries = [ent for ent in reg.entries if id(ent) not in dropped]
-        reg.dirty = True
+    ops.mark_trainable(net)
 
 
 class _HoldConvMath(Function):
@@ -339,43 +76,19 @@ class TrainableUNet(gdp.UNet):
         _thaw(net)
         return net.train()
 
-    def embed(self, emb_in):
-        if not torch.is_grad_enabled():
-            return super().embed(emb_in)
-        n = emb_in.shape[0]
-        e = _conv(emb_in.reshape(n, -1, 1, 1), self.time_embed[0])
-        return silu(_conv(silu(e), self.time_embed[2]))
-
     def forward_embedded(self, x, emb_in):
         if not torch.is_grad_enabled():
             return super().forward_embedded(x, emb_in)
         if ops.get_conv_math() == 'half':                # as the sampler: the U-Net is outside the 16-bit contract, forward AND backward
             with ops.conv_math('bf16x3'):
-                y = self.forward_embedded(x, emb_in)
+                y = self._walk(x, emb_in)
             return _HoldConvMath.apply(y, 'bf16x3')
-        emb_act = self.embed(emb_in)
-        h, hs = x, []
-        for block in self.input_blocks:
-            h = _block_forward(block, h, emb_act)
-            hs.append(h)
-        h = _block_forward(self.middle_block, h, emb_act)
-        for block in self.output_blocks:
-            h = _block_forward(block, ops.cat_channels([h, hs.pop()]), emb_act)
-        return _conv(_norm(h, self.out[0], act=True), self.out[2])
+        return self._walk(x, emb_in)
 
     def forward(self, x, timesteps, y=None):
         if not torch.is_grad_enabled():
             return super().forward(x, timesteps, y)
-        if y is not None:
-            raise NotImplementedError('num_classes: class conditioning is not built')
-        ops._require_gpu(x, 'gdp_train.TrainableUNet')
-        if x.dim() != 4 or x.shape[1] != self.in_channel:
-            raise ValueError('gdp_train.TrainableUNet: input must be [N, %d, H, W], got %s' % (self.in_channel, tuple(x.shape)))
-        down = 2 ** (len(self.channel_mults) - 1)
-        if x.shape[2] % down or x.shape[3] % down:
-            raise ValueError('gdp_train.TrainableUNet: H and W must be multiples of %d, got %d x %d' % (down, x.shape[2], x.shape[3]))
-        emb_in = gdp.timestep_embedding(torch.as_tensor(timesteps), self.model_channels).to(x.device)
-        return self.forward_embedded(ops.nhwc(x), emb_in)
+        return self.forward_embedded(ops.nhwc(x), self._checked_rows('gdp_train.TrainableUNet', x, timesteps, y))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ #
@@ -386,12 +99,6 @@ class TrainableDiffusion(gdp.GaussianDiffusion):
         if self.loss_type not in ('l1', 'l2'):
             raise NotImplementedError('loss_type=%r: l1 and l2 are what the reference names' % (self.loss_type,))
         self.loss_kind = self.loss_type
-
-    def _table(self, device):
-        """Sinusoid rows of every timestep on the device: a step gathers its rows by t, nothing goes through the host."""
-        if self._sinusoid is None or self._sinusoid.device != device:
-            self._sinusoid = gdp.timestep_embedding(torch.arange(self.num_timesteps), self.denoise_fn.model_channels).to(device)
-        return self._sinusoid
 
     def _check_batch(self, x, what):
         ops._require_gpu(x, what)
@@ -411,7 +118,7 @@ class TrainableDiffusion(gdp.GaussianDiffusion):
     def _q_rows(self, x_start, t, noise, seed, step, out):
         t = torch.as_tensor(t).to(device=x_start.device, dtype=torch.int64)
         if noise is None and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())               # a host tensor from torch's CPU generator: no device sync
+            seed = gdp.draw_seed()
         rows = ops.nhwc(x_start).permute(0, 2, 3, 1)
         nrows = None
         if noise is not None:
@@ -450,16 +157,7 @@ class TrainableDiffusion(gdp.GaussianDiffusion):
 
 
 def define_G(opt):
-    """gdp.define_G with the trainable classes."""
-    m = opt['model']
-    if m['which_model_G'] != 'gdp':
-        raise NotImplementedError("which_model_G=%r: only 'gdp' is built (the reference ships no ddpm module)" % m['which_model_G'])
-    u = m['unet']
-    model = TrainableUNet(in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u.get('norm_groups') or 32,
-                          inner_channel=u['inner_channel'], channel_mults=u['channel_multiplier'], attn_res=u['attn_res'],
-                          res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=m['diffusion']['image_size'])
-    return TrainableDiffusion(model, image_size=m['diffusion']['image_size'], channels=m['diffusion']['channels'], loss_type='l2',
-                              conditional=m['diffusion']['conditional'], schedule_opt=m['beta_schedule']['train'])
+    return gdp.build_G(opt, TrainableUNet, TrainableDiffusion)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ #
@@ -510,8 +208,7 @@ class DDPM:
         b, c, h, w = self.data['HR'].shape
         l_pix = self.netG(self.data, noise, t=t, seed=seed) / int(b * c * h * w)
         l_pix.backward()
-        _hip.check(_hip.lib().srhip_adam_step(_p(a.flat_p), _p(a.flat_g), _p(a.exp_avg), _p(a.exp_avg_sq), _p(a.step_state), a.numel, self.lr,
-                                              ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, 1.0, 0.0, _stream()), 'adam_step')
+        a.adam_step(self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS)
         ops.bump_weight_epoch()
         self.steps += 1
         self.log_dict['l_pix'] = l_pix.detach()            # a 0-d device tensor: reading it is the caller's sync, not the step's

@@ -341,6 +341,20 @@ def mark_static(module):
         p._srhip_static = True
 
 
+def mark_trainable(module):
+    """The inverse of mark_static: the static mark goes, and packed images made so far (a frozen net that has run, or one that has
+    trained before) are dropped and leave the batched re-pack, so that the next use packs the weights again and registers them."""
+    dropped = set()
+    for p in module.parameters():
+        dropped.update(id(ent) for ent in getattr(p, '_srhip_packed', {}).values())
+        for attr in ('_srhip_static', '_srhip_packed'):
+            if hasattr(p, attr):
+                delattr(p, attr)
+    if any(id(ent) in dropped for ent in _registry.entries):
+        _registry.entries = [ent for ent in _registry.entries if id(ent) not in dropped]
+        _registry.dirty = True
+
+
 def packed_weight(w, mode):
     """OIHW weight -> GEMM operand.  Parameters get a persistent buffer (see _PackRegistry); other tensors
     (e.g. the weight cotangent of a second-order pass) are packed on the fly."""

@@ -50,18 +50,13 @@ Differences from the reference that do not change results (DESIGN.md "restructur
   * the penalty options (penalty_type, grad_penalty_Lp_norm) only change the scalar function of the interpolate's gradient
     (ops.gp_penalty): the one double backward with weight (1 + lambda_gp) is the same sum for any of them.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _hip, ops
+from . import ops
 from .dp import ParamArena
 from .model.spectral import SpectralNorm, has_spectral_layers
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 _SIDE_STREAMS = {}
@@ -569,11 +564,7 @@ class TrainStep:
         return out
 
     def _adam(self, arena, lr, clip, scale):
-        _hip.check(_hip.lib().srhip_adam_step(_ptr(arena.flat_p), _ptr(arena.flat_g), _ptr(arena.exp_avg),
-                                              _ptr(arena.exp_avg_sq), _ptr(arena.step_state), arena.numel,
-                                              float(lr), float(self.b1), float(self.b2), float(self.eps),
-                                              float(scale), float(clip),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'adam_step')
+        arena.adam_step(lr, self.b1, self.b2, self.eps, scale, clip)
 
     def _update(self):
         """exchange + update: sradsgan.py:858 (optimizer_G.step), :887 (optimizer_D.step), :891-892 (clip).

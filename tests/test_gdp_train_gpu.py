@@ -106,6 +106,34 @@ def test_group_norm_backward_row_strides_of_dy_and_dx(n, p, c):
         assert torch.equal(bits(wide_dx[..., off:c + off]), bits(want[0]))
 
 
+@pytest.mark.parametrize('act', [False, True])
+def test_group_norm_takes_the_halves_of_one_row_without_a_copy(act, monkeypatch):
+    """scale and shift given as the two halves of one [n, 2 C] row reach the kernel as they lie (ldmod = 2 C): the bits of the mod=
+    call, and no concatenation.  Separate tensors are concatenated and give those bits too."""
+    from sradsgan_amd.model import gdp_kernels as K
+    n, p, c = 2, 16, 64
+    x = O.det_fill('gdp.gn.halves.x', (n, p, c), 2.0, 1.5).to(DEV)
+    g, b = O.det_fill('gdp.gn.halves.g', (c,), 0.5, 1.0).to(DEV), O.det_fill('gdp.gn.halves.b', (c,), 0.5).to(DEV)
+    mod = O.det_fill('gdp.gn.halves.mod', (n, 2 * c), 0.5).to(DEV)
+    want = K.group_norm_act(x, g, b, silu=act, mod=mod)
+    apart = K.group_norm_act(x, g, b, mod[:, :c].clone(), mod[:, c:].clone(), silu=act)
+    assert K._one_row(mod[:, :c], mod[:, c:]).data_ptr() == mod.data_ptr() and K._one_row(mod[:, :c].clone(), mod[:, c:]) is None
+
+    def no_cat(*args, **kw):
+        raise AssertionError('group_norm_act concatenated the halves of one row')
+    monkeypatch.setattr(torch, 'cat', no_cat)
+    got = K.group_norm_act(x, g, b, mod[:, :c], mod[:, c:], silu=act)
+    monkeypatch.undo()
+    assert torch.equal(bits(got), bits(want)) and torch.equal(bits(apart), bits(want))
+    assert got.grad_fn is None and float(want.abs().max()) > 0.1
+    # halves that carry a gradient: both of them receive it
+    dy = O.det_fill('gdp.gn.halves.dy', (n, p, c), 1.0).to(DEV)
+    whole, halved = leaf(mod), leaf(mod)
+    K.group_norm_act(x, g, b, silu=act, mod=whole).backward(dy)
+    K.group_norm_act(x, g, b, halved[:, :c], halved[:, c:], silu=act).backward(dy)
+    assert torch.equal(bits(halved.grad), bits(whole.grad)) and float(whole.grad[:, c:].abs().max()) > 0
+
+
 def test_group_norm_backward_refuses_bad_widths():
     from sradsgan_amd import _hip
     lib = _hip.lib()
@@ -277,8 +305,9 @@ def floor(small):
 
 @pytest.mark.parametrize('mode', MODES)
 def test_grad_enabled_forward_has_the_sampler_bits(small, mode):
+    """One walk: the frozen gdp.UNet, the same net adopted by TrainableUNet without grad, and with grad enabled, give the same bits."""
     from sradsgan_amd import ops
-    from sradsgan_amd.model import gdp
+    from sradsgan_amd.model import gdp, gdp_train
     G, _ = small
     net = G.denoise_fn
     twin = R.init_(gdp.UNet(**R.SMALL)).to(DEV)
@@ -293,6 +322,15 @@ def test_grad_enabled_forward_has_the_sampler_bits(small, mode):
     assert y.requires_grad and not want.requires_grad and not quiet.requires_grad
     assert torch.equal(bits(y), bits(want)) and torch.equal(bits(quiet), bits(want))
     assert not any(p.requires_grad for p in twin.parameters())
+    assert want.grad_fn is None and quiet.grad_fn is None
+    adopted = gdp_train.TrainableUNet.adopt(twin)
+    with ops.conv_math(mode):
+        with torch.no_grad():
+            quiet2 = adopted.forward_embedded(x, emb)
+        with torch.enable_grad():
+            y2 = adopted.forward_embedded(x, emb)
+    assert quiet2.grad_fn is None and not quiet2.requires_grad and y2.requires_grad
+    assert torch.equal(bits(quiet2), bits(want)) and torch.equal(bits(y2), bits(want))
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -573,6 +611,30 @@ def test_a_net_that_was_sampled_from_trains_on_fresh_packed_weights(tmp_path):
     registered = {id(ent[0]()) for ent in ops._registry.entries}
     assert all(id(p) in registered for p in net.parameters() if p.dim() >= 2)
     assert model.arena.check_views()
+
+
+def test_mark_trainable_undoes_mark_static_on_a_net_that_has_run():
+    """ops.mark_trainable on a net that was sampled from: no packed image and no static mark stay on its parameters, no live registry
+    entry refers to them, and the next forward packs them again and registers them for the per-step re-pack."""
+    from sradsgan_amd import ops
+    from sradsgan_amd.model import gdp
+    net = R.init_(gdp.UNet(**R.SMALL)).to(DEV)
+    x = ops.nhwc(R.small_input().to(DEV))
+    emb = gdp.timestep_embedding(torch.tensor(T.TRAIN_T), 64).to(DEV)
+    weights = [p for p in net.parameters() if p.dim() >= 2]
+    registered = lambda: {id(ent[0]()) for ent in ops._registry.entries}
+    with ops.conv_math('fp32'):
+        want = net.forward_embedded(x, emb)
+        assert all(hasattr(p, '_srhip_packed') and p._srhip_static for p in weights)
+        assert not any(id(p) in registered() for p in weights)                  # static: packed once, outside the re-pack
+        ops.mark_trainable(net)
+        assert not any(hasattr(p, '_srhip_packed') or hasattr(p, '_srhip_static') for p in net.parameters())
+        assert not any(id(p) in registered() for p in net.parameters())
+        again = net.forward_embedded(x, emb)
+        assert all(hasattr(p, '_srhip_packed') for p in weights) and all(id(p) in registered() for p in weights)
+        assert torch.equal(bits(again), bits(want))
+        ops.mark_trainable(net)                                                  # a net with registered images: they leave the registry
+        assert not any(id(p) in registered() for p in net.parameters()) and ops._registry.dirty
 
 
 # ---- unconditional, and the batch helper ------------------------------------------------------------------------------------------- #

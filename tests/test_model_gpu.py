@@ -353,16 +353,15 @@ def test_train_two_iterations_full_size(golden):
 
 
 def test_adam_kernel_matches_torch():
-    """srhip_adam_step (flat arena, fused clip) vs torch.optim.Adam + clamp_ on identical gradients
-    (sradsgan.py:724-725, 858, 887, 891-892), three steps."""
+    """ParamArena.adam_step (srhip_adam_step over the flat arena, fused clip: the launch every training step shares) vs
+    torch.optim.Adam + clamp_ on identical gradients (sradsgan.py:724-725, 858, 887, 891-892), three steps."""
     from sradsgan_amd.dp import ParamArena
-    from sradsgan_amd.train_step import TrainStep
     torch.manual_seed(3)
     net = torch.nn.Sequential(torch.nn.Conv2d(3, 7, 3), torch.nn.Conv2d(7, 5, 1))
     ref = torch.nn.Sequential(torch.nn.Conv2d(3, 7, 3), torch.nn.Conv2d(7, 5, 1))
     ref.load_state_dict(net.state_dict())
     net.to(DEV)
-    step = TrainStep(net, torch.nn.Linear(1, 1).to(DEV), torch.nn.Linear(1, 1).to(DEV))
+    arena = ParamArena(net)
     opt = torch.optim.Adam(ref.parameters(), lr=2e-4, betas=(0.9, 0.999))
     for it in range(3):
         for (p, q) in zip(net.parameters(), ref.parameters()):
@@ -373,7 +372,7 @@ def test_adam_kernel_matches_torch():
         with torch.no_grad():
             for q in ref.parameters():
                 q.clamp_(-0.05, 0.05)
-        step._adam(step.arena_G, 2e-4, 0.05, 1.0)
+        arena.adam_step(2e-4, 0.9, 0.999, 1e-8, grad_scale=1.0, clip=0.05)
         for (p, q) in zip(net.parameters(), ref.parameters()):
             assert float((p.detach().cpu() - q.detach()).abs().max()) < 2e-7, it
 
