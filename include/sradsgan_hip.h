@@ -513,6 +513,42 @@ int srhip_attn_tail_bwd_pp(const float* dz, const float* u, const float* s, cons
 int srhip_attn_tail_bwd_channel(float* du, const float* davg, const float* dmax, const int* argmax_hw, int n, int h,
                                 int w, int c, void* stream);
 
+/* ---- the attention tail's ablations (sradsgan.py:101-151, 215-324: la_mode x pool_mode); csrc/attn_variants.hip ---------------- *
+ * `order` is the la_mode, `pools` the pool set of both gates (bit 0 Avg, bit 1 Max).  With Chan(a) = sigmoid(sum over the pools
+ * of fc2 relu(fc1 pool_pixels a)) and Spat(a) = sigmoid(conv7x7(the pooled channel maps of a, Avg first, pad 3)):
+ *   CA_SA  s = Chan(u), m = Spat(s u)      SA_CA  m = Spat(u), s = Chan(m u)      CA  s = Chan(u)      SA  m = Spat(u)
+ *   CA_PAR_SA ('CA|SA')  s = Chan(u), m = Spat(u)
+ * u [n][hw][64] NHWC, C == 64, hidden 1..16, w7 [1][|pools|][7][7].  Outputs: avg, mx, s [n][64], arg [n][64] (first pixel attaining
+ * the maximum of the tensor the channel gate pooled), pooled [n][hw][|pools|], argc [n][hw] (first channel), m [n][hw]; those a
+ * variant does not have (no such gate, or a statistic outside the pool set) may be NULL and are not written.  Exact fp32 in every
+ * conv arithmetic, no atomics, fixed reduction order.  The workspace (srhip_attn_var_workspace(n) bytes) is needed by the variants
+ * with a channel gate.  Argument errors return SRHIP_ERR_ARG before any launch.  (Additive: the ABI version does not move.) */
+#define SRHIP_ATTN_CA_SA 0
+#define SRHIP_ATTN_SA_CA 1
+#define SRHIP_ATTN_CA 2
+#define SRHIP_ATTN_SA 3
+#define SRHIP_ATTN_CA_PAR_SA 4
+size_t srhip_attn_var_workspace(int n);
+int srhip_attn_var_fwd(const float* u, const float* fc1, const float* fc2, const float* w7, float* avg, float* mx, int* arg, float* s,
+                       float* pooled, int* argc, float* m, float* ws, size_t ws_bytes, int n, int h, int w, int c, int hidden,
+                       int order, int pools, void* stream);
+/* The closing pass of the variants that do not end in a 64 -> 64 1x1 conv (those hand m and s to srhip_conv2d_fwd as row and channel
+ * scales).  cat == 0: out [n][hw][64] = z + skip with z = m (s u) for CA_SA, s (m u) for SA_CA, s u for CA, m u for SA, each product
+ * and the add rounded once in fp32.  cat != 0 (CA_PAR_SA only): out [n][hw][128] = [s u, m u], the x operand of the 128 -> 64 conv;
+ * skip is not read. */
+int srhip_attn_var_close(const float* u, const float* s, const float* m, const float* skip, float* out, int n, int hw, int c, int order,
+                         int cat, void* stream);
+/* Backward of the same variants: the gradient dz at z ([n][hw][64]; CA_PAR_SA: [n][hw][128], channel half first) and the tensors
+ * srhip_attn_var_fwd saved give du [n][hw][64], dw7 [1][|pools|][7][7], dfc1 [hidden][64], dfc2 [64][hidden]; the parameter gradients
+ * are written, or accumulated into when their flag is set.  Max pools are differentiated at the saved first arg-max indices.  At most
+ * three passes over (dz, u) for the two-gate sequential orders, two for the others; nothing tensor-sized is written but du.  No
+ * atomics, fixed reduction order.  Tensors a variant does not have may be NULL.  Workspace: srhip_attn_var_bwd_workspace() bytes. */
+size_t srhip_attn_var_bwd_workspace(int n, int h, int w, int hidden);
+int srhip_attn_var_bwd(const float* dz, const float* u, const float* s, const float* m, const float* avg, const float* mx, const int* arg,
+                       const float* pooled, const int* argc, const float* w7, const float* fc1, const float* fc2, float* du, float* dw7,
+                       int accumulate_dw7, float* dfc1, float* dfc2, int accumulate_dfc, float* ws, size_t ws_bytes, int n, int h, int w,
+                       int c, int hidden, int order, int pools, void* stream);
+
 /* ---- global attention of GAB_UP (sradsgan.py:365-418), C == 64, NHWC [n][hw][64] ---------------- *
  * CGAM (channel self-attention, sradsgan.py:178-213, light=False; call site :395): E = X^T X per image,
  * A = softmax(rowmax(E) - E), y = gamma * (X A^T) + x.  Exact fp32 on the matrix pipe.  fwd saves A

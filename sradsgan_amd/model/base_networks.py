@@ -8,13 +8,12 @@ from .layers import HipConv2d
 
 
 class _Clam(nn.Module):
-    """sigmoid(MLP(avgpool x) + MLP(maxpool x)) * x with a shared bias-free 1x1 MLP C -> C/ratio -> C."""
+    """sigmoid(sum over the pools in pool_mode of MLP(pool x)) * x with a shared bias-free 1x1 MLP C -> C/ratio -> C."""
 
     def __init__(self, in_planes, ratio=16, pool_mode='Avg|Max'):
         super().__init__()
-        if pool_mode != 'Avg|Max':               # fail at construction, not at the first forward (ops.clam has no single-pool variant)
-            raise NotImplementedError("CLAM / ChannelAttention: only pool_mode 'Avg|Max' is built by the SRADSGAN path "
-                                      "(sradsgan.py:669-671)")
+        if pool_mode not in ops.POOL_MODES:      # fail at construction, not at the first forward
+            raise ValueError("CLAM / ChannelAttention: pool_mode must be 'Avg', 'Max' or 'Avg|Max', got %r" % (pool_mode,))
         self.pool_mode = pool_mode
         self.fc1 = HipConv2d(in_planes, in_planes // ratio, 1, bias=False)
         self.fc2 = HipConv2d(in_planes // ratio, in_planes, 1, bias=False)
@@ -24,16 +23,15 @@ class _Clam(nn.Module):
 
 
 class _Slam(nn.Module):
-    """sigmoid(conv kxk([mean_c x, max_c x])) * x, k in (3, 7), no bias."""
+    """sigmoid(conv kxk(the maps in pool_mode of [mean_c x, max_c x])) * x, k in (3, 7), no bias."""
 
     def __init__(self, kernel_size=7, pool_mode='Avg|Max'):
         super().__init__()
         assert kernel_size in (3, 7), 'kernel size must be 3 or 7'
-        if pool_mode != 'Avg|Max':
-            raise NotImplementedError("SLAM / SpatialAttention: only pool_mode 'Avg|Max' is built by the SRADSGAN path "
-                                      "(sradsgan.py:669-671)")
+        if pool_mode not in ops.POOL_MODES:
+            raise ValueError("SLAM / SpatialAttention: pool_mode must be 'Avg', 'Max' or 'Avg|Max', got %r" % (pool_mode,))
         self.pool_mode = pool_mode
-        self.conv1 = HipConv2d(2, 1, kernel_size, padding=3 if kernel_size == 7 else 1, bias=False)
+        self.conv1 = HipConv2d(2 if pool_mode == 'Avg|Max' else 1, 1, kernel_size, padding=3 if kernel_size == 7 else 1, bias=False)
 
     def forward(self, x):
         return ops.slam(x, self.conv1.weight, self.pool_mode)

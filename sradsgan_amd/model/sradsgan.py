@@ -97,6 +97,13 @@ class _AttentionTail:
                 and ops.attention_tail_supported(out, self.ca.fc1.weight, self.sa.conv1.weight, self.conv.weight)):
             return ops.attention_tail(out, skip, self.ca.fc1.weight, self.ca.fc2.weight, self.sa.conv1.weight,
                                       self.conv.weight, self.conv.bias, emit_pp=emit_pp)
+        ca, sa, conv = getattr(self, 'ca', None), getattr(self, 'sa', None), getattr(self, 'conv', None)
+        fc1, fc2 = (ca.fc1.weight, ca.fc2.weight) if ca is not None else (None, None)
+        w7 = sa.conv1.weight if sa is not None else None
+        if m and ops.attention_variant_supported(out, m, fc1, w7):
+            # every other variant: the gates from csrc/attn_variants.hip, no gated activation written, one autograd node
+            wc, bc = (conv.weight, conv.bias) if conv is not None else (None, None)
+            return ops.attention_variant(out, skip, m, (ca if ca is not None else sa).pool_mode, fc1, fc2, w7, wc, bc)
         if m in ('CA-SA', 'SA-CA'):
             first, second = (self.ca, self.sa) if m == 'CA-SA' else (self.sa, self.ca)
             out = second(first(out))
@@ -106,7 +113,7 @@ class _AttentionTail:
         if m == 'SA':
             return self.sa(out) + skip
         if m == 'CA|SA':
-            return self.conv(torch.cat([self.ca(out), self.sa(out)], dim=1), residual=skip)
+            return self.conv(ops.cat_channels([self.ca(out), self.sa(out)]), residual=skip)
         if m == '':
             return self.last_conv(out, residual=skip)
         return out + skip
@@ -230,7 +237,7 @@ class GAB_UP(nn.Module):
             if self.addconv:
                 out = self.conv(out)
         elif m == 'CA|SA':
-            out = self.conv(torch.cat([self.ca(out), self.sa(out)], dim=1))
+            out = self.conv(ops.cat_channels([self.ca(out), self.sa(out)]))
         return self.upsampling(out)
 
 

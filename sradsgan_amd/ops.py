@@ -1756,6 +1756,138 @@ def attention_tail(u, skip, fc1_w, fc2_w, w7, wc, bc, emit_pp=False):
 
 
 # --------------------------------------------------------------------------------------------- #
+# the tail's ablations (la_mode x pool_mode x addconv, sradsgan.py:215-324): csrc/attn_variants.hip computes the gates s [n,64] and
+# m [n,hw] from u without materialising a gated activation, and the variant closes on the 1x1 conv with m and s as its row and channel
+# scales ('-' modes with addconv), on the gated cat + the 128 -> 64 conv ('CA|SA'), or on one gate-and-add pass.  One autograd node
+# per tail: it saves u and the small statistics; its backward is srhip_attn_var_bwd and the existing 1x1 conv gradients.  With grad
+# mode off the same forward kernels run and nothing is saved, so an eval forward and a training forward have the same bits.
+# --------------------------------------------------------------------------------------------- #
+
+TAIL_ORDERS = {'CA-SA': 0, 'SA-CA': 1, 'CA': 2, 'SA': 3, 'CA|SA': 4}           # SRHIP_ATTN_* of include/sradsgan_hip.h
+_VARIANT_SAVED = ('avg', 'mx', 'arg', 's', 'pooled', 'argc', 'm')
+
+
+def attention_variant_supported(u, la_mode, fc1_w, w7):
+    """The fused route of a non-default tail: C = 64, hidden <= 16, a 7x7 spatial kernel.  fc1_w / w7: None for a variant without
+    that gate.  Otherwise the tail is the composition of the srhip_cbam_* primitives below."""
+    return (la_mode in TAIL_ORDERS and u.is_cuda and u.dtype == torch.float32 and u.shape[1] == 64
+            and (fc1_w is None or fc1_w.shape[0] <= 16) and (w7 is None or tuple(w7.shape[2:]) == (7, 7)))
+
+
+def _det(p):
+    return p.detach().contiguous() if p is not None else None
+
+
+def attention_variant_gates(u, la_mode, pool_mode, fc1_w, fc2_w, w7):
+    """(s [n,64] or None, m [n*hw] or None, the statistics as a dict) of srhip_attn_var_fwd for a dense NHWC u."""
+    n, c, h, w = u.shape
+    lib = _hip.lib()
+    f32, i32 = dict(device=u.device, dtype=torch.float32), dict(device=u.device, dtype=torch.int32)
+    rows = _pool_rows(pool_mode, 'attention_variant')
+    has_c, has_s = 'CA' in la_mode, 'SA' in la_mode
+    t = dict.fromkeys(_VARIANT_SAVED + ('ws',))
+    if has_c:
+        t['s'] = torch.empty(n, c, **f32)
+        t['ws'] = torch.empty(max(lib.srhip_attn_var_workspace(n) // 4, 1), **f32)
+        if 0 in rows:
+            t['avg'] = torch.empty(n, c, **f32)
+        if 1 in rows:
+            t['mx'], t['arg'] = torch.empty(n, c, **f32), torch.empty(n, c, **i32)
+    if has_s:
+        t['pooled'], t['m'] = torch.empty(n * h * w, len(rows), **f32), torch.empty(n * h * w, **f32)
+        if 1 in rows:
+            t['argc'] = torch.empty(n * h * w, **i32)
+    _hip.check(lib.srhip_attn_var_fwd(_p(u), _p(_det(fc1_w)), _p(_det(fc2_w)), _p(_det(w7)), _p(t['avg']), _p(t['mx']), _p(t['arg']),
+                                      _p(t['s']), _p(t['pooled']), _p(t['argc']), _p(t['m']), _p(t['ws']),
+                                      t['ws'].numel() * 4 if has_c else 0, n, h, w, c, fc1_w.shape[0] if has_c else 0,
+                                      TAIL_ORDERS[la_mode], sum(1 << r for r in rows), _stream()), 'attn_var_fwd')
+    return t['s'], t['m'], t
+
+
+def _variant_cat(u, s, m):
+    n, c, h, w = u.shape
+    cat = empty_nhwc(n, 2 * c, h, w, u)
+    _hip.check(_hip.lib().srhip_attn_var_close(_p(u), _p(s), _p(m), None, _p(cat), n, h * w, c, TAIL_ORDERS['CA|SA'], 1, _stream()),
+               'attn_var_close')
+    return cat
+
+
+def _variant_forward(u, skip, la_mode, pool_mode, fc1_w, fc2_w, w7, wc, bc):
+    """(tail(u) + skip, the statistics) for dense NHWC u, skip.  wc / bc: the closing 1x1 conv of the variants that have one ('-' modes
+    with addconv: 64 -> 64; 'CA|SA': 128 -> 64), else None."""
+    n, c, h, w = u.shape
+    s, m, t = attention_variant_gates(u, la_mode, pool_mode, fc1_w, fc2_w, w7)
+    if '-' in la_mode and wc is not None:
+        return conv2d_fwd_raw(u, wc, bc, 1, 0, None, skip, m, s), t          # z = m s u is rebuilt inside the conv, as in _tail_forward
+    if la_mode == 'CA|SA':
+        return conv2d_fwd_raw(_variant_cat(u, s, m), wc, bc, 1, 0, None, skip), t
+    out = torch.empty_like(u, memory_format=CL)
+    _hip.check(_hip.lib().srhip_attn_var_close(_p(u), _p(s), _p(m), _p(skip), _p(out), n, h * w, c, TAIL_ORDERS[la_mode], 0, _stream()),
+               'attn_var_close')
+    return out, t
+
+
+class _VariantTail(Function):
+    @staticmethod
+    def forward(ctx, u, skip, fc1_w, fc2_w, w7, wc, bc, la_mode, pool_mode):
+        u, skip = nhwc(u), nhwc(skip)
+        out, t = _variant_forward(u, skip, la_mode, pool_mode, fc1_w, fc2_w, w7, wc, bc)
+        ctx.la_mode, ctx.pool_mode = la_mode, pool_mode
+        ctx.save_for_backward(u, fc1_w, fc2_w, w7, wc, bc, *[t[k] for k in _VARIANT_SAVED])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        u, fc1_w, fc2_w, w7, wc, bc, avg, mx, arg, s, pooled, argc, m = ctx.saved_tensors
+        g = nhwc(g)
+        mode = ctx.la_mode
+        n, c, h, w = u.shape
+        lib = _hip.lib()
+        f32 = dict(device=u.device, dtype=torch.float32)
+        skip_params = _skip_param_grads()
+        dwc = dbc = None
+        if mode == 'CA|SA':
+            cat = _variant_cat(u, s, m)                               # the conv's x operand, rebuilt: one pass instead of a saved tensor
+            dz = conv2d_dgrad_raw(g, wc, tuple(cat.shape), 1, 0)
+            if not skip_params:
+                dwc, dbc = wgrad_for_params(wc, bc, cat, g, 1, 0, bc is not None)
+        elif '-' in mode and wc is not None:
+            dz = conv2d_dgrad_raw(g, wc, tuple(u.shape), 1, 0)
+            if not skip_params:
+                dwc, dbc = wgrad_for_params(wc, bc, u, g, 1, 0, bc is not None, m, s)       # x operand = z, rebuilt on the fly
+        else:
+            dz = g
+        has_c, has_s = s is not None, m is not None
+        hid = fc1_w.shape[0] if has_c else 0
+        g7 = _grad_slot(w7) if has_s and not skip_params else None
+        g1, g2 = (_grad_slot(fc1_w), _grad_slot(fc2_w)) if has_c and not skip_params else (None, None)
+        direct = g1 is not None and g2 is not None
+        dw7 = g7 if g7 is not None else (torch.empty(w7.shape, **f32) if has_s else None)
+        dfc1 = g1 if direct else (torch.empty(fc1_w.shape, **f32) if has_c else None)
+        dfc2 = g2 if direct else (torch.empty(fc2_w.shape, **f32) if has_c else None)
+        du = torch.empty_like(u, memory_format=CL)
+        ws = torch.empty(lib.srhip_attn_var_bwd_workspace(n, h, w, hid) // 4, **f32)
+        _hip.check(lib.srhip_attn_var_bwd(_p(dz), _p(u), _p(s), _p(m), _p(avg), _p(mx), _p(arg), _p(pooled), _p(argc), _p(_det(w7)),
+                                          _p(_det(fc1_w)), _p(_det(fc2_w)), _p(du), _p(dw7), int(g7 is not None), _p(dfc1), _p(dfc2),
+                                          int(direct), _p(ws), ws.numel() * 4, n, h, w, c, hid, TAIL_ORDERS[mode],
+                                          sum(1 << r for r in _pool_rows(ctx.pool_mode, 'attention_variant')), _stream()), 'attn_var_bwd')
+        if g7 is not None or skip_params:
+            dw7 = None
+        if direct or skip_params:
+            dfc1 = dfc2 = None
+        return du, _passed_through(g), dfc1, dfc2, dw7, dwc, dbc, None, None
+
+
+def attention_variant(u, skip, la_mode, pool_mode, fc1_w, fc2_w, w7, wc, bc):
+    """tail(u) + skip for any la_mode in TAIL_ORDERS (attention_variant_supported): one autograd node, or nothing saved with grad
+    mode off."""
+    _require_gpu(u, 'attention_variant')
+    if not torch.is_grad_enabled():
+        return _variant_forward(nhwc(u), nhwc(skip), la_mode, pool_mode, fc1_w, fc2_w, w7, wc, bc)[0]
+    return _VariantTail.apply(u, skip, fc1_w, fc2_w, w7, wc, bc, la_mode, pool_mode)
+
+
+# --------------------------------------------------------------------------------------------- #
 # channel / spatial attention outside the fused RAB tail: the discriminator's ChannelAttention(256) /
 # SpatialAttention (base_networks.py:366-457, sradsgan.py:495-496) and the stand-alone CLAM / SLAM modules.
 # Built from the srhip_cbam_* primitives, whose backward passes are again primitives: every Function below is
@@ -1957,26 +2089,41 @@ class _SigmoidBwd(Function):
         return dg, dy, None, None
 
 
+POOL_MODES = ('Avg', 'Max', 'Avg|Max')
+
+
+def _pool_rows(pool_mode, what):
+    """indices into the (mean, max) pair of the pooling primitives that `pool_mode` keeps, Avg first like the reference's cat"""
+    if pool_mode not in POOL_MODES:
+        raise ValueError("%s: pool_mode must be one of %s, got %r" % (what, ', '.join(map(repr, POOL_MODES)), pool_mode))
+    return [i for i, name in enumerate(('Avg', 'Max')) if name in pool_mode.split('|')]
+
+
 def clam(x, fc1_w, fc2_w, pool_mode='Avg|Max'):
-    """sradsgan.py:117-127 / base_networks.py:387-403: sigmoid(MLP(avgpool x) + MLP(maxpool x)) * x; the shared
-    bias-free MLP is the reference's two 1x1 convs, applied to the stacked (avg, max) rows in one pass."""
-    if pool_mode != 'Avg|Max':
-        raise NotImplementedError("clam: only pool_mode 'Avg|Max' is built by the SRADSGAN path (sradsgan.py:669-671)")
+    """sradsgan.py:117-127 / base_networks.py:387-403: sigmoid(sum over the pools of MLP(pool x)) * x; the shared bias-free MLP is
+    the reference's two 1x1 convs, applied to the stacked pooled rows in one pass.  A single pool takes its row of the (mean, max)
+    pair: the other row's gradient is zero, so the pooling's adjoint scatters only what the pool saw."""
+    rows_kept = _pool_rows(pool_mode, 'clam')
     n, c = x.shape[0], x.shape[1]
+    k = len(rows_kept)
     t = _PoolHW.apply(x)                                                  # [n,2,c]
-    rows = t.view(2 * n, 1, 1, c).permute(0, 3, 1, 2)                     # logical [2n,c,1,1], NHWC memory: a free view
+    if k == 1:
+        t = t[:, rows_kept[0]].contiguous()                               # [n,c]
+    rows = t.view(k * n, 1, 1, c).permute(0, 3, 1, 2)                     # logical [kn,c,1,1], NHWC memory: a free view
     hid = conv2d(rows, fc1_w, None, 1, 0, act_slope=0.0)                  # ReLU fused
-    logits = conv2d(hid, fc2_w, None, 1, 0)                               # [2n,c,1,1]
-    s = _Sigmoid.apply(logits.permute(0, 2, 3, 1).reshape(n, 2, c), True)  # [n,c]
+    logits = conv2d(hid, fc2_w, None, 1, 0)                               # [kn,c,1,1]
+    s = _Sigmoid.apply(logits.permute(0, 2, 3, 1).reshape(n, k, c) if k == 2 else logits.reshape(n, c), k == 2)   # [n,c]
     return _Scale.apply(x, s, 0)
 
 
 def slam(x, w7, pool_mode='Avg|Max'):
-    """sradsgan.py:141-151 / base_networks.py:440-457: sigmoid(conv kxk([mean_c x, max_c x])) * x."""
-    if pool_mode != 'Avg|Max':
-        raise NotImplementedError("slam: only pool_mode 'Avg|Max' is built by the SRADSGAN path (sradsgan.py:669-671)")
+    """sradsgan.py:141-151 / base_networks.py:440-457: sigmoid(conv kxk(the pooled maps, Avg first)) * x; w7 is [1,1,k,k] for a
+    single pool, as in the reference's checkpoints."""
+    rows_kept = _pool_rows(pool_mode, 'slam')
     n, c, h, w = x.shape
     pooled = _PoolC.apply(x)                                              # [n,2,h,w]
+    if len(rows_kept) == 1:
+        pooled = pooled[:, rows_kept[0]:rows_kept[0] + 1]
     logit = conv2d(pooled, w7, None, 1, w7.shape[-1] // 2)                # [n,1,h,w]
     m = _Sigmoid.apply(logit.reshape(n, h * w), False)
     return _Scale.apply(x, m, 1)

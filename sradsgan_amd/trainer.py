@@ -29,6 +29,7 @@ from . import checkpoint as ckpt
 from . import data as sdata
 from . import dp
 from . import lpips as slpips
+from . import ops
 from . import validate as sval
 from .model import Discriminator, FeatureExtractor, GeneratorResNet, PatchDiscriminator, ResGroup
 from .model.discriminators import NORM_TYPES
@@ -61,6 +62,27 @@ def weights_init_normal(m, mean=0.0, std=0.02):
             m.bias.data.zero_()
 
 
+ATTENTION_MODES = ('',) + tuple(ops.TAIL_ORDERS)       # la_mode / ga_mode of sradsgan.py:215-324, 365-439: '', CA-SA, SA-CA, CA, SA, CA|SA
+POOL_MODES = ops.POOL_MODES
+
+
+def attention_ablation(args):
+    """The generator's attention-ablation switches (sradsgan.py:420-439) read from `args`, absent ones at the values the reference's
+    trainer hard-codes (:669-671): a dict of GeneratorResNet keyword arguments.  A value outside the reference's vocabulary would
+    build a generator that silently has no attention at all (its constructors test `'CA' in mode`), so it is a ValueError here."""
+    opts = dict(rla_mode=getattr(args, 'rla_mode', 'CA-SA'), bla_mode=getattr(args, 'bla_mode', 'CA-SA'),
+                ga_mode=getattr(args, 'ga_mode', 'CA-SA'), pool_mode=getattr(args, 'pool_mode', 'Avg|Max'),
+                addconv=getattr(args, 'addconv', True))
+    for name in ('rla_mode', 'bla_mode', 'ga_mode'):
+        if opts[name] not in ATTENTION_MODES:
+            raise ValueError('args.%s must be one of %r, got %r' % (name, ATTENTION_MODES, opts[name]))
+    if opts['pool_mode'] not in POOL_MODES:
+        raise ValueError('args.pool_mode must be one of %r, got %r' % (POOL_MODES, opts['pool_mode']))
+    if not isinstance(opts['addconv'], bool):
+        raise ValueError('args.addconv must be a bool, got %r' % (opts['addconv'],))
+    return opts
+
+
 class SRADSGAN(object):
     eval_label = 'sradsgan'          # metric key prefix of mfeNew_validate / mfeNew_validateByClass lines (bicubic_* / <label>_*)
 
@@ -79,6 +101,7 @@ class SRADSGAN(object):
             if value not in choices:
                 raise ValueError('--%s must be one of %s, got %r' % (name, choices, value))
         self._check_loss_options()
+        self.attention = attention_ablation(args)
         # the discriminator's normalisation (base_networks.Discriminator's norm_type, the line the reference keeps as a comment at
         # sradsgan.py:672): absent / None = this trainer's own BatchNorm discriminator, else model.discriminators.PatchDiscriminator
         self.d_norm_type = getattr(args, 'd_norm_type', None)
@@ -131,8 +154,7 @@ class SRADSGAN(object):
     # ------------------------------------------------------------------ networks ---------------- #
     def _new_generator(self):
         return GeneratorResNet(ResGroup, n_residual_blocks=self.n_residual_blocks, n_basic_blocks=self.n_basic_blocks,
-                               rla_mode='CA-SA', bla_mode='CA-SA', ga_mode='CA-SA', pool_mode='Avg|Max', addconv=True,
-                               upscale_factor=self.scale_factor)                               # :669-671, :1263-1265
+                               upscale_factor=self.scale_factor, **self.attention)            # :669-671, :1263-1265
 
     def _new_discriminator(self):
         if getattr(self, 'd_spectralnorm', False):
