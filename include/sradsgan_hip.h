@@ -250,6 +250,29 @@ int srhip_conv2d_wgrad_act(const float* x, const float* dy, const float* y, floa
                            void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int kh, int kw,
                            int stride, int pad, int ldx, int ldy, void* stream);
 
+/* Additive in ABI 14 -- the same head conv with an ACTIVATION RECORD: one 64-bit word per output pixel, bit c = (y[pixel][c] > 0)
+ * for the 64 output channels (NaN, +0 and -0 give 0; srhip_conv2d_head_mask_bytes = n * h * w * 8, 8-byte aligned).  The forward
+ * leaves the record behind and the three passes that apply the LeakyReLU's backward read it while they stage the gradient, so
+ * no pass of its own multiplies the 382 MB gradient by the mask and nothing re-reads y:
+ *   srhip_conv2d_fwd_head_mask   mask_out: y = lrelu(conv(x, w) + bias) AND its record (flags = BIAS | LRELU);
+ *                                mask_in:  y = mask * conv(x, w), mask = bit ? 1 : slope (flags = 0): the gradient penalty's second-
+ *                                order pass d_dy = mask * conv(ddx, w).  Exactly one of the two pointers.
+ *   srhip_conv2d_dgrad_head_mask dx = conv_transpose(mask * dy, w)   (packed = the mode-1 packed weight, dense dy)
+ *   srhip_conv2d_wgrad_head_mask dw = wgrad(x, mask * dy), db = column sums of mask * dy (db may be NULL); workspace as
+ *                                srhip_conv2d_wgrad_workspace.
+ * Every result equals, bit for bit, the one of srhip_lrelu_bwd followed by (or following) the plain entry point.
+ * srhip_conv2d_head_mask_ok: 3x3 stride-1 pad-1, cin <= 3, cout == 64, >= 65536 pixels, 3 * (w + 2) * cin * 4 <= 32 KB. */
+int srhip_conv2d_head_mask_ok(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad);
+size_t srhip_conv2d_head_mask_bytes(int n, int h, int w, int cout);
+int srhip_conv2d_fwd_head_mask(const float* x, const float* packed, const float* bias, float* y, void* mask_out, const void* mask_in,
+                               size_t mask_bytes, int n, int h, int w, int cin, int cout, int ldx, int ldy, float slope, int flags,
+                               void* stream);
+int srhip_conv2d_dgrad_head_mask(const float* dy, const float* packed, float* dx, const void* mask, size_t mask_bytes, float slope, int n,
+                                 int h, int w, int cin, int cout, int ldy, int ldx, void* stream);
+int srhip_conv2d_wgrad_head_mask(const float* x, const float* dy, const void* mask, size_t mask_bytes, float slope, float* dw_oihw,
+                                 float* db, void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldx,
+                                 int ldy, void* stream);
+
 /* ---- bias gradient: db[c] = sum_rows dy[row][c]; workspace >= srhip_colsum_workspace() bytes -- */
 size_t srhip_colsum_workspace(long rows, int c);
 int srhip_colsum(const float* dy, float* db, void* workspace, size_t workspace_bytes, long rows, int c,

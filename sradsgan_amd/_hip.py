@@ -57,6 +57,11 @@ SIGNATURES = {
     'srhip_conv2d_wgrad_pp': (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _sz] + [_i] * 6 + [_vp]),
     'srhip_conv2d_wgrad_act_ok': (_i, [_i] * 9),
     'srhip_conv2d_wgrad_act': (_i, [_vp] * 3 + [_f] + [_vp] * 3 + [_sz] + [_i] * 11 + [_vp]),
+    'srhip_conv2d_head_mask_ok': (_i, [_i] * 9),
+    'srhip_conv2d_head_mask_bytes': (_sz, [_i] * 4),
+    'srhip_conv2d_fwd_head_mask': (_i, [_vp] * 6 + [_sz] + [_i] * 7 + [_f, _i, _vp]),
+    'srhip_conv2d_dgrad_head_mask': (_i, [_vp] * 4 + [_sz, _f] + [_i] * 7 + [_vp]),
+    'srhip_conv2d_wgrad_head_mask': (_i, [_vp] * 3 + [_sz, _f] + [_vp] * 3 + [_sz] + [_i] * 7 + [_vp]),
     'srhip_conv2d_wgrad': (_i, [_vp] * 6 + [_i, _vp, _sz] + [_i] * 11 + [_vp]),
     'srhip_colsum_workspace': (_sz, [_l, _i]),
     'srhip_colsum': (_i, [_vp, _vp, _vp, _sz, _l, _i, _i, _vp]),

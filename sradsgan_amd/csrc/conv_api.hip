@@ -561,4 +561,57 @@ int srhip_conv2d_wgrad_act_ok(int n, int h, int w, int cin, int cout, int kh, in
           (size_t)3 * (w + 2) * cin * sizeof(float) <= 32 * 1024) ? 1 : 0;
 }
 
+/* The head conv's ACTIVATION RECORD (sradsgan.py:476: D's 3 -> 64 conv + LeakyReLU at full image size): one 64-bit word per output pixel,
+ * bit c = (y[pixel][c] > 0) -- NaN, +0 and -0 give 0.  The forward leaves it behind and every backward pass of the activation reads it
+ * (1 bit per element) while it stages the gradient, instead of a pass of its own over the gradient and y. */
+int srhip_conv2d_head_mask_ok(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad) {
+  return (cout == 64 && head_conv_shape(n, h, w, cin, kh, kw, stride, pad) && !fast_fwd_ok(cin, cout, kh, kw) && !fast_wgrad_ok(cin, cout, kh, kw) &&
+          fast_dgrad_ok(cin, cout, kh, kw)) ? 1 : 0;
+}
+size_t srhip_conv2d_head_mask_bytes(int n, int h, int w, int cout) {
+  if (n <= 0 || h <= 0 || w <= 0 || cout != 64) return 0;
+  return (size_t)n * h * w * sizeof(unsigned long long);
+}
+static bool head_mask_args(const void* mask, size_t mask_bytes, int n, int h, int w, int cin, int cout) {
+  return mask != nullptr && (((uintptr_t)mask) & 7) == 0 && srhip_conv2d_head_mask_ok(n, h, w, cin, cout, 3, 3, 1, 1) &&
+         mask_bytes >= srhip_conv2d_head_mask_bytes(n, h, w, cout);
+}
+int srhip_conv2d_fwd_head_mask(const float* x, const float* packed, const float* bias, float* y, void* mask_out, const void* mask_in,
+                               size_t mask_bytes, int n, int h, int w, int cin, int cout, int ldx, int ldy, float slope, int flags,
+                               void* stream) {
+  SRHIP_REQUIRE(head_mask_args(mask_out ? mask_out : mask_in, mask_bytes, n, h, w, cin, cout),
+                "conv2d_fwd_head_mask: shape not served (srhip_conv2d_head_mask_ok) / record missing, misaligned or smaller than srhip_conv2d_head_mask_bytes");
+  return legacy_headconv_fwd_mask(x, packed, bias, y, mask_out, mask_in, n, h, w, cin, cout, ldx, ldy, slope, flags, stream);
+}
+int srhip_conv2d_dgrad_head_mask(const float* dy, const float* packed, float* dx, const void* mask, size_t mask_bytes, float slope, int n,
+                                 int h, int w, int cin, int cout, int ldy, int ldx, void* stream) {
+  SRHIP_REQUIRE(dy && packed && dx, "conv2d_dgrad_head_mask: null tensor");
+  SRHIP_REQUIRE(head_mask_args(mask, mask_bytes, n, h, w, cin, cout) && ldy == cout && ldx >= cin,
+                "conv2d_dgrad_head_mask: shape not served (srhip_conv2d_head_mask_ok, dense dy) / record missing, misaligned or too small");
+  g_src_mask_req.words = mask;
+  g_src_mask_req.served = 0;
+  const int rc = fast_conv2d_dgrad(dy, packed, dx, nullptr, nullptr, slope, n, h, w, cin, cout, 3, 3, 1, 1, ldy, ldx, 0, 0, as_stream(stream));
+  const bool served = g_src_mask_req.served != 0;
+  g_src_mask_req = SrcMaskRequest();
+  if (rc != SRHIP_OK) return rc;
+  SRHIP_REQUIRE(served, "conv2d_dgrad_head_mask: the launch that ran does not read the activation record");
+  return SRHIP_OK;
+}
+int srhip_conv2d_wgrad_head_mask(const float* x, const float* dy, const void* mask, size_t mask_bytes, float slope, float* dw, float* db,
+                                 void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldx, int ldy,
+                                 void* stream) {
+  SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_head_mask: null tensor");
+  SRHIP_REQUIRE(head_mask_args(mask, mask_bytes, n, h, w, cin, cout),
+                "conv2d_wgrad_head_mask: shape not served (srhip_conv2d_head_mask_ok) / record missing, misaligned or too small");
+  const size_t need = srhip_conv2d_wgrad_workspace(n, h, w, cin, cout, 3, 3, 1, 1);
+  if (!workspace || workspace_bytes < need) {
+    set_error("conv2d_wgrad_head_mask: workspace %zu bytes < required %zu", workspace_bytes, need);
+    return SRHIP_ERR_WORKSPACE;
+  }
+  const size_t wbytes = align256(legacy_conv2d_wgrad_workspace(n, h, w, cin, cout, 3, 3, 1, 1));
+  int bias_done = 0;
+  return legacy_conv2d_wgrad(x, dy, dw, workspace, wbytes, n, h, w, cin, cout, 3, 3, 1, 1, ldx, ldy, stream, db,
+                             reinterpret_cast<float*>(static_cast<char*>(workspace) + wbytes), &bias_done, nullptr, slope, mask);
+}
+
 }  // extern "C"

@@ -71,6 +71,11 @@ struct Dst2Request {                // rides beside ONE srhip_conv2d_fwd call (c
   int served = 0;
 };
 extern thread_local Dst2Request g_dst2_req;
+struct SrcMaskRequest {             // rides beside ONE srhip_conv2d_dgrad call (conv_api.hip: srhip_conv2d_dgrad_head_mask): the head conv's
+  const void* words = nullptr;      // activation record (one 64-bit word per SOURCE pixel, bit c = channel c's LeakyReLU input was > 0);
+  int served = 0;                   // narrow_conv_kernel multiplies the source values by the mask while it stages them
+};
+extern thread_local SrcMaskRequest g_src_mask_req;
 
 // ================================================================================================ //
 // Debug / experiment knobs: srhip_debug_set(key, value) (conv_api.hip holds the key table).  Every knob is DEFINED in the

@@ -1223,11 +1223,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 //   * the 18 x 18 halo of a 16-channel chunk is staged in LDS (double-buffered, coalesced 16-byte loads,
 //     16-byte slots XOR-swizzled by the pixel index so the nine shifted ds_read_b128 streams are conflict-free);
 //   * weights are indexed uniformly, so they arrive through scalar loads and enter the FMAs as SGPR operands.
+// MASK (64 dense source channels): `smask` holds one 64-bit word per source pixel, bit c = 1 where the LeakyReLU that follows the
+// conv whose data gradient this is let channel c through (headconv_fwd_kernel<1>'s record).  A thread keeps the words of the <= 6
+// pixels it stages and multiplies each staged float4 by the mask of its four channels (v = bit ? v : v * slope) before it goes to
+// LDS: the activation's backward costs 8 bytes per pixel here instead of a pass that reads dy and y and writes g.
 // ================================================================================================ //
-template <int ND>
+template <int ND, bool MASK>
 __global__ __launch_bounds__(256) void narrow_conv_kernel(const float* __restrict__ src, const float* __restrict__ wt,
                                                            const float* __restrict__ bias, float* __restrict__ dst,
-                                                           FastGeom g, int tiles_h, int tiles_w, int lo_h, int lo_w) {
+                                                           FastGeom g, int tiles_h, int tiles_w, int lo_h, int lo_w,
+                                                           const unsigned long long* __restrict__ smask) {
   constexpr int PW = 16, PH = 16, PWP = PW + 2, PR = (PH + 2) * PWP;   // 324 patch rows of 64 B
   __shared__ __attribute__((aligned(16))) float4 lds[2][PR * 4];
   const int tid = threadIdx.x;
@@ -1241,26 +1246,40 @@ __global__ __launch_bounds__(256) void narrow_conv_kernel(const float* __restric
   // staging: 324 rows x 4 quads = 1296 float4 per chunk, 256 threads -> 6 per thread (last partially)
   int soff[6];
   int sdst[6];
+  unsigned long long mw[MASK ? 6 : 1];                 // MASK: the record words of the pixels this thread stages
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     const int e = tid + i * 256;
     soff[i] = -1;
     sdst[i] = 0;
+    if (MASK) mw[i] = 0ull;
     if (e < PR * 4) {
       const int row = e >> 2, q = e & 3;
       const int pi = row / PWP, pj = row - pi * PWP;
       const int sh = oh0 + lo_h + pi, sw = ow0 + lo_w + pj;
       sdst[i] = row * 4 + (q ^ (row & 3));
-      if (sh >= 0 && sh < g.Hs && sw >= 0 && sw < g.Ws) soff[i] = ((img * g.Hs + sh) * g.Ws + sw) * g.lds + q * 4;
-      else soff[i] = -2;                               // inside the patch, outside the image: zero
+      if (sh >= 0 && sh < g.Hs && sw >= 0 && sw < g.Ws) {
+        soff[i] = ((img * g.Hs + sh) * g.Ws + sw) * g.lds + q * 4;
+        if (MASK) mw[i] = smask[(img * g.Hs + sh) * g.Ws + sw];
+      } else {
+        soff[i] = -2;                                  // inside the patch, outside the image: zero
+      }
     }
   }
   const int CC = g.C / 16;
   float4 stage[6];
   auto fetch = [&](int cc) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < 6; ++i) {
       stage[i] = soff[i] >= 0 ? *reinterpret_cast<const float4*>(src + (size_t)soff[i] + cc * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (MASK) {                                      // channels cc * 16 + q * 4 .. + 3 of the pixel (q = tid & 3 for every i); zeros stay zero
+        const unsigned b = (unsigned)(mw[i] >> (cc * 16 + (tid & 3) * 4));
+        stage[i].x = (b & 1u) ? stage[i].x : stage[i].x * g.slope;
+        stage[i].y = (b & 2u) ? stage[i].y : stage[i].y * g.slope;
+        stage[i].z = (b & 4u) ? stage[i].z : stage[i].z * g.slope;
+        stage[i].w = (b & 8u) ? stage[i].w : stage[i].w * g.slope;
+      }
+    }
   };
   auto commit = [&](int buf) {
 #pragma unroll
@@ -1399,6 +1418,7 @@ int fast_pack_weight(const float* w, float* packed, int cout, int cin, int kh, i
 thread_local Dst2Request g_dst2_req;
 thread_local ResRequest g_res_req;
 thread_local PhaseRequest g_phase_req;
+thread_local SrcMaskRequest g_src_mask_req;
 int g_conv_math = 0;     // SRHIP_MATH_*: 0 exact fp32 MFMA; 1 split-bf16 x3 MFMA; 2 one 16-bit product (fp16 activations / bf16 gradients)
 int g_patch_ks = 1;      // srhip_debug_set(10, v): 0 = conv_patch_kernel<64> instead of conv_patch_ks_kernel (bit-identical to the DMA kernel; A/B and pinned tests)
 int g_fast_cfg = 0;      // srhip_debug_set(0, cfg): a FastCfg value (conv_dev.h), 0 = the heuristic of choose_fprop_route
@@ -1701,8 +1721,14 @@ static int launch_fprop(const ConvOperands& a, const FastGeom& g, const FpropRou
     case FpropFamily::Narrow: {
       const int th = cdiv(g.OH, 16), tw = cdiv(g.OW, 16);
       const int lo_h = g.dhs > 0 ? g.dh0 : g.dh0 + 2 * g.dhs, lo_w = g.dws > 0 ? g.dw0 : g.dw0 + 2 * g.dws;
-      auto k = r.nd == 3 ? narrow_conv_kernel<3> : narrow_conv_kernel<4>;
-      hipLaunchKernelGGL(k, dim3(g.N * th * tw), dim3(256), 0, st, a.src, a.wt, a.bias, a.dst, g, th, tw, lo_h, lo_w);
+      const unsigned long long* smask = nullptr;
+      if (g_src_mask_req.words != nullptr && g.C == 64 && g.lds == 64) {    // srhip_conv2d_dgrad_head_mask
+        smask = static_cast<const unsigned long long*>(g_src_mask_req.words);
+        g_src_mask_req.served = 1;
+      }
+      auto k = smask ? (r.nd == 3 ? narrow_conv_kernel<3, true> : narrow_conv_kernel<4, true>)
+                     : (r.nd == 3 ? narrow_conv_kernel<3, false> : narrow_conv_kernel<4, false>);
+      hipLaunchKernelGGL(k, dim3(g.N * th * tw), dim3(256), 0, st, a.src, a.wt, a.bias, a.dst, g, th, tw, lo_h, lo_w, smask);
       return check_launch("narrow_conv");
     }
     case FpropFamily::Dot:

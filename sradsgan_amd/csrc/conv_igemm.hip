@@ -17,9 +17,10 @@
 // from 32x32 MFMA tiles.  LDS images are k-major so that a wave's MFMA operand fetch is 32
 // consecutive dwords per half-wave (conflict-free ds_read_b32).
 #include "common.h"
+#include "conv_internal.h"
 
 namespace srhip {
-int g_headconv_rows = 4;   // srhip_debug_set(18, rows): image rows a block of headconv_fwd_kernel walks
+int g_headconv_rows = 4;  // srhip_debug_set(18, rows): image rows a block of headconv_fwd_kernel walks
 }
 namespace srhip {
 
@@ -413,8 +414,15 @@ __global__ __launch_bounds__(256) void igemm_wgrad_kernel(const float* __restric
 // K = 9*Cin <= 27 pads to 32 = sixteen 32x32x2 fp32 MFMA steps; the whole weight matrix (32 x 64) lives in registers.
 // A block takes one image row: the three input rows (zero halo) are staged in LDS, a wave owns 32 consecutive output
 // pixels x 64 channels, gathers its A values from LDS and stores 128-byte channel runs.  Write-bound by design.
+// MASK (cout == 64 only; `rec` = one 64-bit word per output pixel, bit c = (y[pixel][c] > 0), NaN and both zeros give 0):
+//   1: the epilogue also WRITES the record of its output -- per pixel the ballots of the two accumulator halves, one 256-byte store
+//      per wave and 32 pixels -- so that the backward passes of the fused LeakyReLU read 1 bit per element instead of y;
+//   2: the epilogue READS a record and multiplies by the mask, v = bit ? v : v * slope (the activation's backward applied to this
+//      conv's output: the second-order pass of the gradient penalty, d_dy = mask * conv(ddx, w)), no other activation.
+template <int MASK>
 __global__ __launch_bounds__(256) void headconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ packed,
                                                             const float* __restrict__ bias, float* __restrict__ y,
+                                                            unsigned long long* __restrict__ rec,
                                                             int N, int H, int W, int cin, int cout, int ldx, int ldy,
                                                             int ldw, float slope, int flags, int rows_per_block) {
   extern __shared__ float xs[];                      // [3][W + 2][cin]
@@ -460,6 +468,14 @@ __global__ __launch_bounds__(256) void headconv_fwd_kernel(const float* __restri
     f32x16 acc0, acc1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+    // the record word of pixel ow0 + l31, as two dwords (both half-waves hold the same 32 words): MASK 2 loads it here, one coalesced
+    // 256-byte read per wave whose latency the gathers and MFMAs below cover; MASK 1 collects it from the ballots of the epilogue
+    unsigned wlo = 0u, whi = 0u;
+    if (MASK == 2 && ow0 + l31 < W) {
+      const unsigned long long m = rec[(size_t)r * W + ow0 + l31];
+      wlo = (unsigned)m;
+      whi = (unsigned)(m >> 32);
+    }
 #pragma unroll
     for (int s_ = 0; s_ < 16; ++s_) {
       const float a = koff[s_] >= 0 ? xs[p * cin + koff[s_]] : 0.f;
@@ -468,18 +484,33 @@ __global__ __launch_bounds__(256) void headconv_fwd_kernel(const float* __restri
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int ow = ow0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+      const int px = (i & 3) + 8 * (i >> 2);          // accumulator i: pixel ow0 + px in lanes 0-31, ow0 + px + 4 in lanes 32-63
+      const int ow = ow0 + px + 4 * half;
+      float v0 = acc0[i] + b0, v1 = acc1[i] + b1;
+      if (MASK == 2) {                                // (all lanes are active here: the lane reads below need no exec care)
+        const unsigned lo = half ? (unsigned)__builtin_amdgcn_readlane((int)wlo, px + 4) : (unsigned)__builtin_amdgcn_readlane((int)wlo, px);
+        const unsigned hi = half ? (unsigned)__builtin_amdgcn_readlane((int)whi, px + 4) : (unsigned)__builtin_amdgcn_readlane((int)whi, px);
+        v0 = ((lo >> l31) & 1u) ? v0 : v0 * slope;
+        v1 = ((hi >> l31) & 1u) ? v1 : v1 * slope;
+      } else if (flags & SRHIP_EPI_LRELU) {
+        v0 = v0 > 0.f ? v0 : v0 * slope;
+        v1 = v1 > 0.f ? v1 : v1 * slope;
+      }
+      if (MASK == 1) {
+        // lanes 0-31 hold channels 0-31 (v0) and 32-63 (v1) of one pixel, lanes 32-63 those of the pixel four columns on: the low
+        // dwords of the two ballots are the first pixel's word, the high dwords the second's; lane px (px + 4) keeps it
+        const unsigned long long q0 = __ballot(v0 > 0.f), q1 = __ballot(v1 > 0.f);
+        wlo = l31 == px ? (unsigned)q0 : (l31 == px + 4 ? (unsigned)(q0 >> 32) : wlo);
+        whi = l31 == px ? (unsigned)q1 : (l31 == px + 4 ? (unsigned)(q1 >> 32) : whi);
+      }
       if (ow < W) {
-        float v0 = acc0[i] + b0, v1 = acc1[i] + b1;
-        if (flags & SRHIP_EPI_LRELU) {
-          v0 = v0 > 0.f ? v0 : v0 * slope;
-          v1 = v1 > 0.f ? v1 : v1 * slope;
-        }
         float* o = y + ((size_t)r * W + ow) * ldy + co0 + l31;
         if (co0 + l31 < cout) o[0] = v0;
         if (co0 + 32 + l31 < cout) o[32] = v1;
       }
     }
+    if (MASK == 1 && lane < 32 && ow0 + lane < W)     // one coalesced store of the group's <= 32 words
+      rec[(size_t)r * W + ow0 + lane] = ((unsigned long long)whi << 32) | wlo;
   }
   }
 }
@@ -497,8 +528,12 @@ __global__ __launch_bounds__(256) void headconv_fwd_kernel(const float* __restri
 // (dy * (y > 0 ? 1 : slope)) is applied to the values as they are loaded, so the separate lrelu-backward pass over the
 // 382 MB gradient (read dy, read y, write g: 150 us in the discriminator's serial chain, three passes per step) is not
 // needed when only the weight gradient of the layer is wanted.
+// BITS (cout == 64): the same mask from the head conv's activation record instead of y (headconv_fwd_kernel<1>: one 64-bit word per
+// pixel, bit c = y[pixel][c] > 0) -- 8 bytes per pixel beside the 256 of dy, where y cost another 256.
+template <bool BITS>
 __global__ __launch_bounds__(256) void wgrad_smallcin_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                              const float* __restrict__ ymask, float slope,
+                                                              const float* __restrict__ ymask,
+                                                              const unsigned long long* __restrict__ ybits, float slope,
                                                               float* __restrict__ partial, float* __restrict__ bias_partial,
                                                               int N, int H, int W, int cin,
                                                               int cout, int ldx, int ldy, int rows_per_split) {
@@ -532,14 +567,19 @@ __global__ __launch_bounds__(256) void wgrad_smallcin_kernel(const float* __rest
     }
     __syncthreads();
     const float* drow = dy + (size_t)r * W * ldy + co0 + l31;
-    const float* yrow = ymask ? ymask + (size_t)r * W * ldy + co0 + l31 : nullptr;
+    const float* yrow = (!BITS && ymask) ? ymask + (size_t)r * W * ldy + co0 + l31 : nullptr;
+    const unsigned long long* brow = BITS ? ybits + (size_t)r * W : nullptr;
 #pragma unroll 4
     for (int ow = 2 * wave; ow < W; ow += 8) {       // this wave's pixel pairs (ow, ow + 1)
       const int p = ow + half;
       const bool pok = p < W;
       float d0 = (pok && c0ok) ? drow[(size_t)p * ldy] : 0.f;
       float d1 = (pok && c1ok) ? drow[(size_t)p * ldy + 32] : 0.f;
-      if (yrow != nullptr) {
+      if (BITS) {
+        const unsigned long long m = pok ? brow[p] : ~0ull;
+        if (!((m >> l31) & 1ull)) d0 *= slope;
+        if (!((m >> (32 + l31)) & 1ull)) d1 *= slope;
+      } else if (yrow != nullptr) {
         if (pok && c0ok && !(yrow[(size_t)p * ldy] > 0.f)) d0 *= slope;
         if (pok && c1ok && !(yrow[(size_t)p * ldy + 32] > 0.f)) d1 *= slope;
       }
@@ -844,14 +884,42 @@ int legacy_conv2d_fwd(const float* x, const float* packed, const float* bias, co
   long M = (long)n * g.Ho * g.Wo;
   SRHIP_REQUIRE(M < (1L << 31) && (long)n * h * w < (1L << 31), "conv2d_fwd: pixel count overflows int32");
   g.M = (int)M; g.slope = slope; g.flags = flags; g.accumulate = 0;
-  if (cin <= 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && M >= 65536 &&
-      !(flags & ~(SRHIP_EPI_BIAS | SRHIP_EPI_LRELU)) && (size_t)3 * (w + 2) * cin * sizeof(float) <= 32 * 1024) {
+  if (head_conv_shape(n, h, w, cin, kh, kw, stride, pad) && !(flags & ~(SRHIP_EPI_BIAS | SRHIP_EPI_LRELU))) {
     const int rpb = g_headconv_rows > 0 ? g_headconv_rows : 1;
-    hipLaunchKernelGGL(headconv_fwd_kernel, dim3(cdiv((long)n * h, rpb), cdiv(cout, 64)), dim3(256), (size_t)3 * (w + 2) * cin * sizeof(float),
-                       as_stream(stream), x, packed, bias, y, n, h, w, cin, cout, ldx, ldy, g.ldw, slope, flags, rpb);
+    hipLaunchKernelGGL(headconv_fwd_kernel<0>, dim3(cdiv((long)n * h, rpb), cdiv(cout, 64)), dim3(256), (size_t)3 * (w + 2) * cin * sizeof(float),
+                       as_stream(stream), x, packed, bias, y, (unsigned long long*)nullptr, n, h, w, cin, cout, ldx, ldy, g.ldw, slope, flags, rpb);
     return check_launch("headconv_fwd");
   }
   return run_fprop(x, packed, bias, residual, rowscale, y, g, as_stream(stream));
+}
+
+// the shapes headconv_fwd_kernel / wgrad_smallcin_kernel take: 3x3 stride-1 pad-1, <= 3 input channels, a full-size image whose three
+// staged rows fit 32 KB of LDS
+bool head_conv_shape(int n, int h, int w, int cin, int kh, int kw, int stride, int pad) {
+  return n > 0 && h > 0 && w > 0 && cin > 0 && cin <= 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && (long)n * h * w >= 65536 &&
+         (long)n * h * w < (1L << 31) && (size_t)3 * (w + 2) * cin * sizeof(float) <= 32 * 1024;
+}
+
+// The head conv with its activation record (conv_api.hip: srhip_conv2d_fwd_head_mask): rec_out = the record of y = lrelu(conv + bias)
+// is written beside y; rec_in = y = mask * conv(x, w) with the mask read from a record.  Exactly one of the two; 64 output channels.
+int legacy_headconv_fwd_mask(const float* x, const float* packed, const float* bias, float* y, void* rec_out, const void* rec_in, int n,
+                             int h, int w, int cin, int cout, int ldx, int ldy, float slope, int flags, void* stream) {
+  SRHIP_REQUIRE(x && packed && y && ((rec_out != nullptr) != (rec_in != nullptr)), "conv2d_fwd_head_mask: null tensor / exactly one of mask_out, mask_in");
+  SRHIP_REQUIRE(head_conv_shape(n, h, w, cin, 3, 3, 1, 1) && cout == 64 && ldx >= cin && ldy >= cout,
+                "conv2d_fwd_head_mask: shape not served (srhip_conv2d_head_mask_ok)");
+  SRHIP_REQUIRE(rec_out ? (flags == (SRHIP_EPI_BIAS | SRHIP_EPI_LRELU) && bias != nullptr) : flags == 0,
+                "conv2d_fwd_head_mask: mask_out goes with bias + LeakyReLU, mask_in with a plain epilogue");
+  const int rpb = g_headconv_rows > 0 ? g_headconv_rows : 1;
+  const dim3 grid(cdiv((long)n * h, rpb), 1);
+  const size_t lds = (size_t)3 * (w + 2) * cin * sizeof(float);
+  const int ldw = legacy_packed_ld(cout);
+  if (rec_out)
+    hipLaunchKernelGGL(headconv_fwd_kernel<1>, grid, dim3(256), lds, as_stream(stream), x, packed, bias, y, static_cast<unsigned long long*>(rec_out),
+                       n, h, w, cin, cout, ldx, ldy, ldw, slope, flags, rpb);
+  else
+    hipLaunchKernelGGL(headconv_fwd_kernel<2>, grid, dim3(256), lds, as_stream(stream), x, packed, bias, y,
+                       static_cast<unsigned long long*>(const_cast<void*>(rec_in)), n, h, w, cin, cout, ldx, ldy, ldw, slope, flags, rpb);
+  return check_launch("headconv_fwd_mask");
 }
 
 int legacy_conv2d_dgrad(const float* dy, const float* packed, float* dx, int n, int h, int w, int cin, int cout,
@@ -897,11 +965,13 @@ size_t legacy_conv2d_wgrad_bias_workspace(int n, int h, int w, int cin, int cout
 // legacy_conv2d_wgrad_bias_workspace bytes) and set *bias_done; otherwise the caller runs the column-sum pass.
 int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes, int n,
                        int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int ldx, int ldy,
-                       void* stream, float* db, float* bias_ws, int* bias_done, const float* ymask, float slope) {
+                       void* stream, float* db, float* bias_ws, int* bias_done, const float* ymask, float slope, const void* ybits) {
   if (bias_done) *bias_done = 0;
   SRHIP_REQUIRE(!ymask || (db && bias_ws && bias_done && cin <= 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 &&
                            (long)n * h * w >= 65536 && (size_t)3 * (w + 2) * cin * sizeof(float) <= 32 * 1024),
                 "conv2d_wgrad: the fused activation mask is built for the 3-channel 3x3 head convs at full image size (with bias)");
+  SRHIP_REQUIRE(!ybits || (!ymask && cout == 64 && head_conv_shape(n, h, w, cin, kh, kw, stride, pad)),
+                "conv2d_wgrad: the activation record is built for the 3-channel 3x3 head convs to 64 channels at full image size");
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad: null tensor");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                 "conv2d_wgrad: bad geometry");
@@ -931,8 +1001,13 @@ int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* worksp
     const int rps = cdiv(rows, ns);
     ns = cdiv(rows, rps);
     const bool fuse_bias = db != nullptr && bias_ws != nullptr && bias_done != nullptr;
-    hipLaunchKernelGGL(wgrad_smallcin_kernel, dim3(ns, cdiv(cout, 64)), dim3(256), (size_t)32 * 1024, st,
-                       x, dy, ymask, slope, partial, fuse_bias ? bias_ws : nullptr, n, h, w, cin, cout, ldx, ldy, rps);
+    if (ybits)
+      hipLaunchKernelGGL(wgrad_smallcin_kernel<true>, dim3(ns, 1), dim3(256), (size_t)32 * 1024, st, x, dy, (const float*)nullptr,
+                         static_cast<const unsigned long long*>(ybits), slope, partial, fuse_bias ? bias_ws : nullptr, n, h, w, cin, cout, ldx,
+                         ldy, rps);
+    else
+      hipLaunchKernelGGL(wgrad_smallcin_kernel<false>, dim3(ns, cdiv(cout, 64)), dim3(256), (size_t)32 * 1024, st, x, dy, ymask,
+                         (const unsigned long long*)nullptr, slope, partial, fuse_bias ? bias_ws : nullptr, n, h, w, cin, cout, ldx, ldy, rps);
     int rc0 = check_launch("wgrad_smallcin");
     if (rc0) return rc0;
     long total0 = (long)cout * g.Ktot;

@@ -17,7 +17,12 @@ size_t legacy_conv2d_wgrad_bias_workspace(int n, int h, int w, int cin, int cout
 int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes, int n,
                         int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int ldx, int ldy,
                         void* stream, float* db = nullptr, float* bias_ws = nullptr, int* bias_done = nullptr,
-                        const float* ymask = nullptr, float slope = 0.f);
+                        const float* ymask = nullptr, float slope = 0.f, const void* ybits = nullptr);
+// the head conv (3x3 stride-1 pad-1, <= 3 input channels, full-size image) and its activation record: one 64-bit word per output
+// pixel, bit c = (y[pixel][c] > 0), 64 output channels (include/sradsgan_hip.h: srhip_conv2d_head_mask_*)
+bool head_conv_shape(int n, int h, int w, int cin, int kh, int kw, int stride, int pad);
+int legacy_headconv_fwd_mask(const float* x, const float* packed, const float* bias, float* y, void* rec_out, const void* rec_in, int n,
+                             int h, int w, int cin, int cout, int ldx, int ldy, float slope, int flags, void* stream);
 
 // ---- fast path (conv_fast_fprop.hip / conv_wgrad_fast.hip): source channels % 16 == 0, <= 32 taps ------------------------- //
 // fprop/dgrad eligibility depends only on the conv's static shape, so the packed-weight layout

@@ -530,6 +530,47 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride, pad, residual=None, actmask=None, s
     return dx
 
 
+_HEAD_BITS = os.environ.get('SRHIP_HEAD_BITS', '1') == '1'    # A/B knob: 0 = the head conv's LeakyReLU backward runs as passes of its own over the gradient and y
+
+
+def head_mask_ok(x_shape, w_shape, stride, pad):
+    """The head conv (3 -> 64, 3x3, full image size) whose forward can leave its activation record behind (srhip_conv2d_head_mask_ok)."""
+    n, cin, h, wd = x_shape
+    cout, _, kh, kw = w_shape
+    return bool(_hip.lib().srhip_conv2d_head_mask_ok(n, h, wd, cin, cout, kh, kw, stride, pad))
+
+
+def conv2d_fwd_head_mask_raw(x, w, bias, slope, bits=None):
+    """bits None: (y, record) with y = lrelu(conv(x, w) + bias) and the record of y > 0, one 64-bit word per pixel.
+    bits given: y = mask * conv(x, w) (no bias), mask = 1 where the record's bit is set, else slope."""
+    _require_gpu(x, 'conv2d_fwd_head_mask')
+    x = nhwc(x)
+    n, cin, h, wd = x.shape
+    cout = w.shape[0]
+    y = empty_nhwc(n, cout, h, wd, x)
+    lib = _hip.lib()
+    made = bits is None
+    if made:
+        bits = torch.empty(n * h * wd, device=x.device, dtype=torch.int64)
+        bias = bias.detach().contiguous()
+    _hip.check(lib.srhip_conv2d_fwd_head_mask(_p(x), _p(packed_weight(w, 0)), _p(bias) if made else None, _p(y), _p(bits) if made else None,
+                                              None if made else _p(bits), bits.numel() * 8, n, h, wd, cin, cout, cin, cout, float(slope),
+                                              (EPI_BIAS | EPI_LRELU) if made else 0, _stream()), 'conv2d_fwd_head_mask')
+    return (y, bits) if made else y
+
+
+def conv2d_dgrad_head_mask_raw(dy, w, x_shape, bits, slope):
+    """dx = conv_transpose(mask * dy, w): the head conv's data gradient from the gradient at its ACTIVATED output."""
+    _require_gpu(dy, 'conv2d_dgrad_head_mask')
+    dy = nhwc(dy)
+    n, cin, h, wd = x_shape
+    cout = w.shape[0]
+    dx = empty_nhwc(n, cin, h, wd, dy)
+    _hip.check(_hip.lib().srhip_conv2d_dgrad_head_mask(_p(dy), _p(packed_weight(w, 1)), _p(dx), _p(bits), bits.numel() * 8, float(slope),
+                                                       n, h, wd, cin, cout, cout, cin, _stream()), 'conv2d_dgrad_head_mask')
+    return dx
+
+
 _SIDE_WS = {}
 
 
@@ -557,11 +598,13 @@ def _wgrad_tables(items):
     return [tab(*col) for col in cols]
 
 
-def conv2d_wgrad_raw(x, dy, w_shape, stride, pad, with_bias=False, xrowscale=None, xchanscale=None, out=None, on_stream=None):
+def conv2d_wgrad_raw(x, dy, w_shape, stride, pad, with_bias=False, xrowscale=None, xchanscale=None, out=None, on_stream=None, head_bits=None):
     """(dw [OIHW], db [Cout] or None): the bias gradient comes out of the same kernel pass.
     out=(dw_buf, db_buf or None): accumulate into these buffers instead (dw_buf += dw, db_buf += db).
     on_stream: launch on this torch stream (already ordered behind the operands' producers by the caller) instead of the
-    current one, with that stream's persistent workspace."""
+    current one, with that stream's persistent workspace.
+    head_bits=(record, slope): dy is the gradient at the head conv's ACTIVATED output; the kernel multiplies it by the LeakyReLU mask
+    of the record as it reads it (srhip_conv2d_wgrad_head_mask)."""
     _require_gpu(x, 'conv2d_wgrad')
     x, dy = nhwc(x), nhwc(dy)
     n, cin, h, wd = x.shape
@@ -573,6 +616,13 @@ def conv2d_wgrad_raw(x, dy, w_shape, stride, pad, with_bias=False, xrowscale=Non
         db = torch.empty(cout, device=x.device, dtype=torch.float32) if with_bias else None
     else:
         dw, db = out
+    if head_bits is not None:
+        if out is not None or xrowscale is not None or xchanscale is not None or (kh, kw, stride, pad) != (3, 3, 1, 1):
+            raise ValueError('conv2d_wgrad: the activation record goes with the plain 3x3 head conv, not accumulated')
+        bits, slope = head_bits
+        _hip.check(lib.srhip_conv2d_wgrad_head_mask(_p(x), _p(dy), _p(bits), bits.numel() * 8, float(slope), _p(dw), _p(db), _p(ws),
+                                                    ws.numel() * 4, n, h, wd, cin, cout, cin, cout, st), 'conv2d_wgrad_head_mask')
+        return dw, db
     _hip.check(lib.srhip_conv2d_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(xrowscale), _p(xchanscale), int(out is not None), _p(ws),
                                       ws.numel() * 4, n, h, wd, cin, cout, kh, kw, stride, pad, cin, cout, st), 'conv2d_wgrad')
     return dw, db
@@ -992,18 +1042,19 @@ def wgrad_pp_for_params(w, b, x, dy, want_b, release=()):
     return True
 
 
-def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscale=None):
+def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscale=None, head_bits=None):
     """(dw, db) to return to autograd for parameters (w, b).  In direct_param_grads() mode the kernel
-    accumulates into w.grad / b.grad, on the weight-gradient stream (_WgradQueue), and this returns (None, None)."""
+    accumulates into w.grad / b.grad, on the weight-gradient stream (_WgradQueue), and this returns (None, None).
+    head_bits=(record, slope): dy is the gradient at the head conv's activated output (conv2d_wgrad_raw)."""
     cout, cin, kh, kw = w.shape
     gw = _grad_slot(w)
     gb = _grad_slot(b) if (want_b and b is not None) else None
     if gw is None or (want_b and gb is None):
-        return conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
+        return conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, head_bits=head_bits)
     q = _state.wgrads
     x, dy = nhwc(x), nhwc(dy)
     lib = _hip.lib()
-    if lib.srhip_conv2d_wgrad_can_accumulate(cin, cout, kh, kw):
+    if head_bits is None and lib.srhip_conv2d_wgrad_can_accumulate(cin, cout, kh, kw):
         q.tick()
         job = q.job(x, dy, gw, gb, stride, pad)
         if (q.group > 1 and xrowscale is None and xchanscale is None
@@ -1023,11 +1074,11 @@ def wgrad_for_params(w, b, x, dy, stride, pad, want_b, xrowscale=None, xchanscal
     # follows per-thread node counters (tests/test_graph_gpu.py) -- and, like the other weight gradients, on the side
     # stream: the 3 -> 64 head convs' gradients (0.2 - 0.3 ms each at 216 x 216) sat in the discriminator's serial chain
     def launch(_):
-        dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale)
+        dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), stride, pad, want_b, xrowscale, xchanscale, head_bits=head_bits)
         gw.add_(dw)
         if db is not None:
             gb.add_(db)
-    q.run([q.job(x, dy, gw, gb, stride, pad)], launch, extra=(xrowscale, xchanscale))
+    q.run([q.job(x, dy, gw, gb, stride, pad)], launch, extra=(xrowscale, xchanscale, head_bits[0] if head_bits is not None else None))
     return None, None
 
 
@@ -1142,17 +1193,48 @@ class _ConvFwd(Function):
     def forward(ctx, x, w, b, residual, stride, pad, slope, graddata=False):
         if slope is not None and residual is not None:
             raise ValueError('conv2d: fused activation and residual are mutually exclusive')
-        y = conv2d_fwd_raw(x, w, b, stride, pad, slope, residual, graddata=graddata)
+        bits = None
+        if (_HEAD_BITS and slope is not None and b is not None and not graddata and x.is_cuda and any(ctx.needs_input_grad[:3])
+                and head_mask_ok(x.shape, w.shape, stride, pad)):
+            # D's head conv with a backward to come: the forward leaves the activation record behind (1 bit per element of y), and the
+            # kernels that consume the gradient at y apply the LeakyReLU mask from it -- no lrelu-backward pass, no re-read of y
+            y, bits = conv2d_fwd_head_mask_raw(x, w, b, slope)
+        else:
+            y = conv2d_fwd_raw(x, w, b, stride, pad, slope, residual, graddata=graddata)
         ctx.stride, ctx.pad, ctx.slope = stride, pad, slope
         ctx.has_bias, ctx.has_res = b is not None, residual is not None
-        ctx.save_for_backward(x, w, y if slope is not None else None, b)
+        ctx.save_for_backward(x, w, y if slope is not None else None, b, bits)
         return y
 
     @staticmethod
+    def _backward_head_bits(ctx, dy, x, w, y, b, bits, need_dx, skip):
+        """The backward of the head conv from its activation record; None where the record has no kernel for what is wanted (the caller
+        then runs the passes over y)."""
+        want_w = ctx.needs_input_grad[1] and not skip
+        want_b = ctx.needs_input_grad[2] and not skip
+        if want_b and not want_w:
+            return None
+        if torch.is_grad_enabled():                    # create_graph: the gradient penalty's first-order pass
+            if want_w or not need_dx:
+                return None
+            return _HeadDgradMasked.apply(dy, w, y.detach(), bits, tuple(x.shape), ctx.slope), None, None, None, None, None, None, None
+        dx = conv2d_dgrad_head_mask_raw(dy, w, tuple(x.shape), bits, ctx.slope) if need_dx else None
+        dw = db = None
+        if want_w and _state.wgrads is not None:
+            dw, db = wgrad_for_params(w, b, x, dy, ctx.stride, ctx.pad, want_b, head_bits=(bits, ctx.slope))
+        elif want_w:
+            dw, db = conv2d_wgrad_raw(x, dy, tuple(w.shape), ctx.stride, ctx.pad, want_b, head_bits=(bits, ctx.slope))
+        return dx, dw, db, None, None, None, None, None
+
+    @staticmethod
     def backward(ctx, dy):
-        x, w, y, b = ctx.saved_tensors
+        x, w, y, b, bits = ctx.saved_tensors
         skip = _skip_param_grads(w)
         need_dx = ctx.needs_input_grad[0] and x.data_ptr() not in _state.stop_ids
+        if bits is not None:
+            out = _ConvFwd._backward_head_bits(ctx, dy, x, w, y, b, bits, need_dx, skip)
+            if out is not None:
+                return out
         if ctx.slope is not None and not need_dx and not skip and ctx.needs_input_grad[1] and ctx.has_bias and \
                 ctx.needs_input_grad[2] and _state.wgrads is not None and not torch.is_grad_enabled() and \
                 _wgrad_act_direct(w, b, x, dy, y, ctx.slope, ctx.stride, ctx.pad):
@@ -1193,6 +1275,51 @@ class _ConvDgrad(Function):
         elif ctx.needs_input_grad[1] and not skip:
             d_w, _ = _ConvWgrad.apply(ddx, dy, tuple(w.shape), ctx.stride, ctx.pad, False)
         return d_dy, d_w, None, None, None
+
+
+class _HeadDgradMasked(Function):
+    """dx = conv_transpose(m * dy, w) with m = LeakyReLU'(y) read from the head conv's activation record: bilinear in (dy, w), the mask
+    is a constant.  One node where _LReluBwd and _ConvDgrad stood, and neither m * dy nor the second-order m * conv(ddx, w) is ever
+    a tensor of its own: the kernels on both sides apply the mask in registers.  `y` rides along for a third-order graph only."""
+
+    @staticmethod
+    def forward(ctx, dy, w, y, bits, x_shape, slope):
+        ctx.x_shape, ctx.slope = x_shape, slope
+        ctx.save_for_backward(dy, w, y, bits)
+        return conv2d_dgrad_head_mask_raw(dy, w, x_shape, bits, slope)
+
+    @staticmethod
+    def backward(ctx, ddx):
+        dy, w, y, bits = ctx.saved_tensors
+        skip = _skip_param_grads(w)
+        d_dy = _HeadFwdMasked.apply(ddx, w, y, bits, ctx.slope) if ctx.needs_input_grad[0] else None
+        d_w = None
+        if ctx.needs_input_grad[1] and not skip and torch.is_grad_enabled():
+            d_w, _ = _ConvWgrad.apply(ddx, _LReluBwd.apply(dy, y, ctx.slope), tuple(w.shape), 1, 1, False)
+        elif ctx.needs_input_grad[1] and not skip and _state.wgrads is not None:
+            d_w, _ = wgrad_for_params(w, None, ddx, dy, 1, 1, False, head_bits=(bits, ctx.slope))   # same stream/order as every other wgrad of w
+        elif ctx.needs_input_grad[1] and not skip:
+            d_w, _ = conv2d_wgrad_raw(ddx, dy, tuple(w.shape), 1, 1, False, head_bits=(bits, ctx.slope))
+        return d_dy, d_w, None, None, None, None
+
+
+class _HeadFwdMasked(Function):
+    """d_dy = m * conv(ddx, w): the adjoint of _HeadDgradMasked in dy, the mask applied in the head conv kernel's epilogue."""
+
+    @staticmethod
+    def forward(ctx, ddx, w, y, bits, slope):
+        ctx.slope = slope
+        ctx.save_for_backward(ddx, w, y, bits)
+        return conv2d_fwd_head_mask_raw(ddx, w, None, slope, bits=bits)
+
+    @staticmethod
+    def backward(ctx, g):
+        ddx, w, y, bits = ctx.saved_tensors
+        d_ddx = _HeadDgradMasked.apply(g, w, y, bits, tuple(ddx.shape), ctx.slope) if ctx.needs_input_grad[0] else None
+        d_w = None
+        if ctx.needs_input_grad[1] and not _skip_param_grads(w):
+            d_w, _ = _ConvWgrad.apply(ddx, _LReluBwd.apply(g, y, ctx.slope), tuple(w.shape), 1, 1, False)
+        return d_ddx, d_w, None, None, None
 
 
 class _ConvWgrad(Function):
