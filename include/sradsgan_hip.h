@@ -350,7 +350,9 @@ int srhip_batch_sum_scaled(const float* g, float scale, float* out, int n, long 
  *   srhip_hat_combine_fwd : HAB's out = (x + kb[b] a) + cs (s[b,c] u); kb NULL: 1; u NULL: no third term (the MLP branch)
  *   srhip_hat_combine_bwd : da = kb[b] g; with u: du = cs s g + d(mean)/hw through the channel attention and its parameter
  *                        gradients dw1 [hidden][C], db1, dw2 [C][hidden], db2 (written, images summed in order; NULL: not written);
- *                        workspace >= srhip_hat_combine_bwd_workspace(n, C, hidden).  dx = g is the caller's.             */
+ *                        workspace >= srhip_hat_combine_bwd_workspace(n, C, hidden).  dx = g is the caller's.
+ * Argument errors return SRHIP_ERR_ARG, a NULL or too small workspace SRHIP_ERR_WORKSPACE, both before any launch and with a
+ * message that names the entry point.                                                                                          */
 int srhip_hat_ln_parts(long tokens);
 int srhip_hat_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long tokens,
                      void* stream);
@@ -576,7 +578,8 @@ int srhip_attn_var_bwd(const float* dz, const float* u, const float* s, const fl
  * CGAM (channel self-attention, sradsgan.py:178-213, light=False; call site :395): E = X^T X per image,
  * A = softmax(rowmax(E) - E), y = gamma * (X A^T) + x.  Exact fp32 on the matrix pipe.  fwd saves A
  * (att [n][64][64]); bwd returns dx (incl. the residual path) and dgamma (accumulate_dgamma != 0: +=).
- * Both need srhip_cgam_workspace() bytes of scratch.                                                  */
+ * Both need srhip_cgam_workspace() bytes of 16-byte aligned scratch.  Every tensor but dgamma is required:
+ * a NULL one is SRHIP_ERR_ARG, a NULL or too small workspace SRHIP_ERR_WORKSPACE, before any launch.  */
 size_t srhip_cgam_workspace(int n, int hw);
 int srhip_cgam_fwd(const float* x, const float* gamma, float* y, float* att, void* workspace, size_t workspace_bytes,
                    int n, int hw, int c, void* stream);
@@ -587,7 +590,8 @@ int srhip_cgam_bwd(const float* dy, const float* x, const float* att, const floa
  * no 1/sqrt(d) scaling.  Flash-style: the hw x hw energy / attention matrices (torch.bmm + Softmax, :167-172) are
  * never written to memory; fwd saves o = softmax(.) v [n][hw][64] and the per-query log-sum-exp lse [n][hw];
  * bwd recomputes the probabilities (deterministic two-pass, no atomics) and returns dq, dk, dv and dgamma; the
- * gradient of the residual path is dy itself.  bwd needs srhip_sgam_flash_bwd_workspace() bytes.        */
+ * gradient of the residual path is dy itself.  bwd needs srhip_sgam_flash_bwd_workspace() bytes.  Every
+ * tensor but dgamma is required (NULL: SRHIP_ERR_ARG; workspace NULL or too small: SRHIP_ERR_WORKSPACE).  */
 int srhip_sgam_flash_fwd(const float* q, const float* k, const float* v, const float* x, const float* gamma, float* y,
                          float* o, float* lse, int n, int hw, int dk, int c, void* stream);
 size_t srhip_sgam_flash_bwd_workspace(int n, int hw);

@@ -959,7 +959,9 @@ int srhip_cgam_fwd(const float* x, const float* gamma, float* y, float* att, voi
                    int n, int hw, int c, void* stream) {
   SRHIP_REQUIRE(c == GA_C, "cgam_fwd: C must be 64 (sradsgan.py:194), got %d", c);
   SRHIP_REQUIRE(n > 0 && hw > 0, "cgam_fwd: empty input");
-  SRHIP_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)att) & 15) == 0, "cgam_fwd: pointers must be 16-byte aligned");
+  SRHIP_REQUIRE(x && gamma && y && att, "cgam_fwd: null tensor");
+  SRHIP_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)att | (uintptr_t)workspace) & 15) == 0,
+                "cgam_fwd: pointers must be 16-byte aligned");
   if (!workspace || workspace_bytes < srhip_cgam_workspace(n, hw)) {
     set_error("cgam_fwd: workspace %zu bytes < required %zu", workspace_bytes, srhip_cgam_workspace(n, hw));
     return SRHIP_ERR_WORKSPACE;
@@ -977,7 +979,9 @@ int srhip_cgam_bwd(const float* dy, const float* x, const float* att, const floa
                    int accumulate_dgamma, void* workspace, size_t workspace_bytes, int n, int hw, int c, void* stream) {
   SRHIP_REQUIRE(c == GA_C, "cgam_bwd: C must be 64, got %d", c);
   SRHIP_REQUIRE(n > 0 && hw > 0, "cgam_bwd: empty input");
-  SRHIP_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)att) & 15) == 0, "cgam_bwd: pointers must be 16-byte aligned");
+  SRHIP_REQUIRE(dy && x && att && gamma && dx, "cgam_bwd: null tensor (only dgamma may be NULL)");
+  SRHIP_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)att | (uintptr_t)workspace) & 15) == 0,
+                "cgam_bwd: pointers must be 16-byte aligned");
   if (!workspace || workspace_bytes < srhip_cgam_workspace(n, hw)) {
     set_error("cgam_bwd: workspace %zu bytes < required %zu", workspace_bytes, srhip_cgam_workspace(n, hw));
     return SRHIP_ERR_WORKSPACE;
@@ -998,6 +1002,7 @@ int srhip_sgam_flash_fwd(const float* q, const float* k, const float* v, const f
                          float* o, float* lse, int n, int hw, int dk, int c, void* stream) {
   SRHIP_REQUIRE(c == GA_C && dk == GA_DK, "sgam_flash_fwd: C must be 64 and q/k channels 8 (sradsgan.py:157-159), got %d / %d", c, dk);
   SRHIP_REQUIRE(n > 0 && hw > 0, "sgam_flash_fwd: empty input");
+  SRHIP_REQUIRE(q && k && v && x && gamma && y && o && lse, "sgam_flash_fwd: null tensor");
   SRHIP_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)x | (uintptr_t)y | (uintptr_t)o) & 15) == 0,
                 "sgam_flash_fwd: pointers must be 16-byte aligned");
   if (ga_split_math())
@@ -1018,6 +1023,7 @@ int srhip_sgam_flash_bwd(const float* dy, const float* q, const float* k, const 
                          void* workspace, size_t workspace_bytes, int n, int hw, int dk, int c, void* stream) {
   SRHIP_REQUIRE(c == GA_C && dk == GA_DK, "sgam_flash_bwd: C must be 64 and q/k channels 8, got %d / %d", c, dk);
   SRHIP_REQUIRE(n > 0 && hw > 0, "sgam_flash_bwd: empty input");
+  SRHIP_REQUIRE(dy && q && k && v && o && lse && gamma && dq && dk_ && dv, "sgam_flash_bwd: null tensor (only dgamma may be NULL)");
   SRHIP_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dy | (uintptr_t)o | (uintptr_t)dq | (uintptr_t)dk_ | (uintptr_t)dv) & 15) == 0,
                 "sgam_flash_bwd: pointers must be 16-byte aligned");
   if (!workspace || workspace_bytes < srhip_sgam_flash_bwd_workspace(n, hw)) {

@@ -473,7 +473,7 @@ static int attn_bwd_launch(const float* qkv, const float* table, const float* ou
   const size_t need = attn_ws_bytes<OCA, WS>(nwin);
   if (ws_bytes < need) {
     set_error("hat_attn_bwd: workspace %zu bytes < required %zu", ws_bytes, need);
-    return SRHIP_ERR_ARG;
+    return SRHIP_ERR_WORKSPACE;
   }
   float* part = static_cast<float*>(ws);
   const size_t part_bytes = ((size_t)HAT_HEADS * nblk * G::NQ * G::NK * 4 + 255) & ~(size_t)255;
@@ -707,20 +707,20 @@ int srhip_hat_gelu_bwd(const float* dy, const float* x, float* dx, long count, v
   return check_launch("hat_gelu_bwd");
 }
 
-static int attn_check(int kind, int n, int h, int w, int ws, int shift) {
-  SRHIP_REQUIRE(kind == 0 || kind == 1, "hat_attn: kind 0 (SA) or 1 (OCA)");
-  SRHIP_REQUIRE(ws == 8 || ws == 9, "hat_attn: window 8 or 9, got %d", ws);
-  SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && h % ws == 0 && w % ws == 0, "hat_attn: %d x %d is not a multiple of the window %d", h,
-                w, ws);
-  SRHIP_REQUIRE(shift == 0 || (kind == 0 && shift == ws / 2), "hat_attn: shift 0 or ws / 2 (SA only), got %d", shift);
-  SRHIP_REQUIRE((long)n * (h / ws) * (w / ws) < (1L << 31), "hat_attn: too many windows");
+static int attn_check(const char* who, int kind, int n, int h, int w, int ws, int shift) {
+  SRHIP_REQUIRE(kind == 0 || kind == 1, "%s: kind 0 (SA) or 1 (OCA)", who);
+  SRHIP_REQUIRE(ws == 8 || ws == 9, "%s: window 8 or 9, got %d", who, ws);
+  SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && h % ws == 0 && w % ws == 0, "%s: %d images of %d x %d are not multiples of the window %d",
+                who, n, h, w, ws);
+  SRHIP_REQUIRE(shift == 0 || (kind == 0 && shift == ws / 2), "%s: shift 0 or ws / 2 (SA only), got %d", who, shift);
+  SRHIP_REQUIRE((long)n * (h / ws) * (w / ws) < (1L << 31), "%s: too many windows", who);
   return SRHIP_OK;
 }
 
 int srhip_hat_attn_fwd(const float* qkv, const float* table, float* out, float* lse, int kind, int n, int h, int w, int ws, int shift,
                        void* stream) {
   SRHIP_REQUIRE(qkv && table && out && lse && aligned16(qkv), "hat_attn_fwd: bad arguments");
-  int rc = attn_check(kind, n, h, w, ws, shift);
+  int rc = attn_check("hat_attn_fwd", kind, n, h, w, ws, shift);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   if (kind == 0) return ws == 9 ? attn_fwd_launch<0, 9>(qkv, table, out, lse, n, h, w, shift, st)
@@ -739,10 +739,14 @@ size_t srhip_hat_attn_bwd_workspace(int kind, int n, int h, int w, int ws) {
 int srhip_hat_attn_bwd(const float* qkv, const float* table, const float* out, const float* dout, const float* lse, float* dqkv,
                        float* dtable, void* workspace, size_t workspace_bytes, int kind, int n, int h, int w, int ws, int shift,
                        void* stream) {
-  SRHIP_REQUIRE(qkv && table && out && dout && lse && dqkv && dtable && workspace && aligned16(qkv) && aligned16(workspace),
+  SRHIP_REQUIRE(qkv && table && out && dout && lse && dqkv && dtable && aligned16(qkv) && aligned16(workspace),
                 "hat_attn_bwd: bad arguments");
-  int rc = attn_check(kind, n, h, w, ws, shift);
+  int rc = attn_check("hat_attn_bwd", kind, n, h, w, ws, shift);
   if (rc) return rc;
+  if (!workspace) {
+    set_error("hat_attn_bwd: workspace is NULL");
+    return SRHIP_ERR_WORKSPACE;
+  }
   hipStream_t st = as_stream(stream);
   if (kind == 0)
     return ws == 9 ? attn_bwd_launch<0, 9>(qkv, table, out, dout, lse, dqkv, dtable, workspace, workspace_bytes, n, h, w, shift, st)
@@ -751,16 +755,16 @@ int srhip_hat_attn_bwd(const float* qkv, const float* table, const float* out, c
                  : attn_bwd_launch<1, 8>(qkv, table, out, dout, lse, dqkv, dtable, workspace, workspace_bytes, n, h, w, 0, st);
 }
 
-static int ca_check(int n, long hw, int c, int hid) {
+static int ca_check(const char* who, int n, long hw, int c, int hid) {
   SRHIP_REQUIRE(n > 0 && hw > 0 && c % 4 == 0 && c >= 4 && c <= HAT_CA_MAXC && hid >= 1 && hid <= HAT_CA_MAXHID,
-                "hat_ca: C %% 4 == 0, C <= %d, 1 <= hidden <= %d (got %d, %d)", HAT_CA_MAXC, HAT_CA_MAXHID, c, hid);
+                "%s: C %% 4 == 0, C <= %d, 1 <= hidden <= %d (got %d, %d)", who, HAT_CA_MAXC, HAT_CA_MAXHID, c, hid);
   return SRHIP_OK;
 }
 
 int srhip_hat_ca_fwd(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* mz, int n,
                      long hw, int c, int hid, void* stream) {
   SRHIP_REQUIRE(u && w1 && w2 && s && mz && aligned16(u), "hat_ca_fwd: bad arguments");
-  int rc = ca_check(n, hw, c, hid);
+  int rc = ca_check("hat_ca_fwd", n, hw, c, hid);
   if (rc) return rc;
   hat_ca_fwd_kernel<<<n, 256, 0, as_stream(stream)>>>(u, w1, b1, w2, b2, s, mz, hw, c, hid);
   return check_launch("hat_ca_fwd");
@@ -792,11 +796,14 @@ int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const
                                                            reinterpret_cast<float4*>(da), nullptr, cs, quads, per, c / 4, 0, 0);
     return check_launch("hat_combine_bwd");
   }
-  int rc = ca_check(n, hw, c, hid);
+  int rc = ca_check("hat_combine_bwd", n, hw, c, hid);
   if (rc) return rc;
-  SRHIP_REQUIRE(u && s && mz && w1 && w2 && workspace && aligned16(u) && aligned16(s) && aligned16(du) && aligned16(workspace),
+  SRHIP_REQUIRE(u && s && mz && w1 && w2 && aligned16(u) && aligned16(s) && aligned16(du) && aligned16(workspace),
                 "hat_combine_bwd: bad channel-attention arguments");
-  SRHIP_REQUIRE(workspace_bytes >= srhip_hat_combine_bwd_workspace(n, c, hid), "hat_combine_bwd: workspace too small");
+  if (!workspace || workspace_bytes < srhip_hat_combine_bwd_workspace(n, c, hid)) {
+    set_error("hat_combine_bwd: workspace %zu bytes < required %zu", workspace_bytes, srhip_hat_combine_bwd_workspace(n, c, hid));
+    return SRHIP_ERR_WORKSPACE;
+  }
   float* scratch = static_cast<float*>(workspace);
   hat_ca_bwd_kernel<<<n, 256, 0, st>>>(g, u, s, mz, w1, w2, scratch, cs, hw, c, hid);
   rc = check_launch("hat_ca_bwd");
