@@ -384,7 +384,8 @@ int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const
  *   srhip_scaled_res_bwd   : dc = ka * dz (dc non-NULL); dr[0:ch] = kb * dz + kc * e (e optional), dr[ch:width] = 0 (dr non-NULL):
  *                            the gradient at the conv and the initial gradient of a dense-block buffer in one pass.
  *   srhip_lrelu_bwd_strided: dx = dy * (y > 0 ? 1 : slope) over ch channels (in place when dx == dy): the CL's LeakyReLU(0.2)
- *                            backward, the mask from the post-activation values in the buffer.
+ *                            backward, the mask from the post-activation values in the buffer.  dy and dx have one row stride
+ *                            (ldx == ldg), in place or not; anything else is SRHIP_ERR_ARG.
  *   srhip_upsample_nearest_fwd / _bwd: nn.UpsamplingNearest2d(r), r in {2, 3}, NHWC [n, h, w, c] <-> [n, r h, r w, c]; the backward
  *                            sums each r x r block in a fixed order (no atomics).                                                  */
 int srhip_scaled_res_fwd(const float* r, int ldr, const float* c, int ldc, const float* s, int lds, float alpha, float beta, float* y,

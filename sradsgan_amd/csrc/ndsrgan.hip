@@ -150,7 +150,7 @@ int srhip_lrelu_bwd_strided(const float* dy, int ldg, const float* y, int ldy, f
   SRHIP_REQUIRE(dy && y && dx && rows > 0 && ch > 0 && ch % 4 == 0, "lrelu_bwd_strided: bad arguments");
   SRHIP_REQUIRE(ldg >= ch && ldy >= ch && ldx >= ch && (ldg | ldy | ldx) % 4 == 0, "lrelu_bwd_strided: row strides");
   SRHIP_REQUIRE(al16(dy) && al16(y) && al16(dx), "lrelu_bwd_strided: 16-byte aligned tensors");
-  SRHIP_REQUIRE(dx == dy || ldx == ldg, "lrelu_bwd_strided: in place or separate tensors of one row stride");
+  SRHIP_REQUIRE(ldx == ldg, "lrelu_bwd_strided: dy and dx must have one row stride, in place (dx == dy) or not");
   const long total = rows * (ch / 4);
   hipLaunchKernelGGL(lrelu_bwd_strided_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), dy, ldg, y, ldy, dx, ldx, slope,
                      rows, ch / 4);
