@@ -374,6 +374,36 @@ size_t srhip_hat_combine_bwd_workspace(int n, int c, int hidden);
 int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
                           const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
                           size_t workspace_bytes, float cs, int n, long hw, int c, int hidden, void* stream);
+/* ABI 14, additive -- HAT at its published widths (csrc/hat_wide.hip; the channel attention in csrc/hat.hip): embed_dim C = 144 or
+ * 180, heads of 24 or 30 channels, window 16 with overlap 0.5 (key window 24 x 24, padding 4).  The contracts are those of the
+ * srhip_hat_* entries above with the width, the head count and the window as arguments; srhip_hat_gelu_* and srhip_hat_combine_fwd
+ * take any width and serve both families.  Exact fp32 whatever the conv arithmetic mode, no atomics, fixed-order reductions.
+ *   srhip_hatw_ln_fwd / _bwd : nn.LayerNorm(C) (eps 1e-5), 128 < C <= 192, C % 4 == 0; part: [srhip_hatw_ln_parts(tokens)][2C]
+ *   srhip_hatw_attn_fwd : qkv [n*h*w][3C] (part * C + head * D + d), D = C / heads = 24 or 30, 1 to 6 heads, ws = 16, h and w multiples of 16,
+ *                        shift 0 or 8 (kind 0 only); table [961 (kind 0) or 1521 (kind 1)][heads]; out [n*h*w][C], lse [n*h*w][heads].
+ *                        qkv, out, dout, dqkv and the workspace are 16-byte aligned.
+ *   srhip_hatw_attn_bwd : dqkv and dtable (written); workspace >= srhip_hatw_attn_bwd_workspace(kind, n, h, w, C, heads, ws) holds
+ *                        the table-gradient partials by table row, delta = rowsum(dO o O) and, for kind 1, the per-window dk / dv
+ *                        slabs -- never an element per (query, key) pair.
+ *   srhip_hatw_ca_fwd / srhip_hatw_combine_bwd : srhip_hat_ca_fwd / srhip_hat_combine_bwd at 128 < C <= 192 (workspace:
+ *                        srhip_hat_combine_bwd_workspace).
+ * Anything else returns SRHIP_ERR_ARG (SRHIP_ERR_WORKSPACE for a NULL or too small workspace) before any launch. */
+int srhip_hatw_ln_parts(long tokens);
+int srhip_hatw_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long tokens, int c,
+                      void* stream);
+int srhip_hatw_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dadd,
+                      float* dx, float* part, float* dgamma, float* dbeta, long tokens, int c, void* stream);
+int srhip_hatw_attn_fwd(const float* qkv, const float* table, float* out, float* lse, int kind, int n, int h, int w, int c, int heads,
+                        int ws, int shift, void* stream);
+size_t srhip_hatw_attn_bwd_workspace(int kind, int n, int h, int w, int c, int heads, int ws);
+int srhip_hatw_attn_bwd(const float* qkv, const float* table, const float* out, const float* dout, const float* lse, float* dqkv,
+                        float* dtable, void* workspace, size_t workspace_bytes, int kind, int n, int h, int w, int c, int heads, int ws,
+                        int shift, void* stream);
+int srhip_hatw_ca_fwd(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* mz, int n,
+                      long hw, int c, int hidden, void* stream);
+int srhip_hatw_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
+                           const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                           size_t workspace_bytes, float cs, int n, long hw, int c, int hidden, void* stream);
 /* ABI 13 -- NDSRGAN (model/ndsrgan.py:57-211).  Rows are pixels; every operand has its own row stride (floats, multiple of 4, >= ch),
  * all pointers 16-byte aligned, ch % 4 == 0.  A dense block keeps its input and the four CL outputs in ONE [n, h, w, 192] buffer:
  * CL j reads channels 0 : 64+32j (srhip_conv2d_fwd ldx = 192) and writes 64+32j : 96+32j (ldy = 192), and the passes below write a

@@ -201,6 +201,14 @@ SIGNATURES = {
     'srhip_hat_combine_fwd': (_i, [_vp] * 6 + [_f, _i, _l, _i, _vp]),
     'srhip_hat_combine_bwd_workspace': (_sz, [_i] * 3),
     'srhip_hat_combine_bwd': (_i, [_vp] * 14 + [_sz, _f, _i, _l, _i, _i, _vp]),
+    'srhip_hatw_ln_parts': (_i, [_l]),
+    'srhip_hatw_ln_fwd': (_i, [_vp] * 6 + [_l, _i, _vp]),
+    'srhip_hatw_ln_bwd': (_i, [_vp] * 10 + [_l, _i, _vp]),
+    'srhip_hatw_attn_fwd': (_i, [_vp] * 4 + [_i] * 8 + [_vp]),
+    'srhip_hatw_attn_bwd_workspace': (_sz, [_i] * 7),
+    'srhip_hatw_attn_bwd': (_i, [_vp] * 8 + [_sz] + [_i] * 8 + [_vp]),
+    'srhip_hatw_ca_fwd': (_i, [_vp] * 7 + [_i, _l, _i, _i, _vp]),
+    'srhip_hatw_combine_bwd': (_i, [_vp] * 14 + [_sz, _f, _i, _l, _i, _i, _vp]),
     'srhip_adam_step': (_i, [_vp] * 5 + [_l] + [_f] * 6 + [_vp]),
     'srhip_sn_entry_bytes': (_i, []),
     'srhip_sn_tpart_elems': (_l, [_i, _i]),

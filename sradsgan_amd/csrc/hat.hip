@@ -11,7 +11,8 @@
 //     block's LDS (one row per thread) and folds it into the table gradient in a fixed order; OCA's overlapping dK / dV go to
 //     per-window slabs that a gather pass folds per pixel in a fixed order;
 //   * HAB's combine out = x + k_b a + cs (s[b,c] u) (drop-path factor k_b, channel-attention scale s of CAB's output u) with the
-//     channel attention at any C <= 128 (hidden <= 16, with biases), and its backward.
+//     channel attention at any C <= 128 (hidden <= 16, with biases), and its backward; the same kernels with 384 threads serve the
+//     published widths 128 < C <= 192 (srhip_hatw_ca_fwd / srhip_hatw_combine_bwd; the rest of that family is hat_wide.hip).
 // fp32 throughout; no atomics: every result is bit-identical from run to run.
 #include "common.h"
 
@@ -24,6 +25,7 @@ constexpr int HAT_QKV = 3 * HAT_C; // qkv row
 constexpr float HAT_LN_EPS = 1e-5f;
 constexpr int HAT_BWD_BLOCKS = 64; // attention backward: most blocks per head (each walks windows g, g + G, ...)
 constexpr int HAT_CA_MAXC = 128, HAT_CA_MAXHID = 16;
+constexpr int HAT_CA_WIDE_MAXC = 192;   // the published widths (144, 180): 8 pixel lanes x C / 4 quads need 384 threads
 
 // ---------------------------------------------------------------------------------------------------------------------------- //
 // LayerNorm: one wave per token, lane l holds channels l and 64 + l (l < 32)
@@ -499,9 +501,9 @@ static int attn_bwd_launch(const float* qkv, const float* table, const float* ou
 // ---------------------------------------------------------------------------------------------------------------------------- //
 
 // per image: sum over the pixels of a[p,c] (PROD: a[p,c] b[p,c]) by 8 pixel lanes x C/4 channel quads, lanes combined in order
-template <bool PROD>
+template <bool PROD, int MAXC>
 __device__ void chan_sum(const float* __restrict__ a, const float* __restrict__ b, long hw, int c, float* __restrict__ out,
-                         float4 (*red)[HAT_CA_MAXC / 4]) {
+                         float4 (*red)[MAXC / 4]) {
   const int cq = c / 4, q = threadIdx.x % cq, r = threadIdx.x / cq;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (r < 8) {
@@ -531,14 +533,16 @@ __device__ void chan_sum(const float* __restrict__ a, const float* __restrict__ 
 }
 
 // one block per image: m = mean_hw u, z = relu(w1 m + b1), s = sigmoid(w2 z + b2); mz[b] = [m (c) | z (hid)]
-__global__ __launch_bounds__(256) void hat_ca_fwd_kernel(const float* __restrict__ u, const float* __restrict__ w1,
-                                                         const float* __restrict__ b1, const float* __restrict__ w2,
-                                                         const float* __restrict__ b2, float* __restrict__ s,
-                                                         float* __restrict__ mz, long hw, int c, int hid) {
-  __shared__ float4 red[8][HAT_CA_MAXC / 4];
-  __shared__ float sm[HAT_CA_MAXC], sz[HAT_CA_MAXHID];
+// (MAXC 128: 256 threads; MAXC 192: 384 threads, so that every channel quad has its 8 pixel lanes)
+template <int MAXC>
+__global__ __launch_bounds__(2 * MAXC) void hat_ca_fwd_kernel(const float* __restrict__ u, const float* __restrict__ w1,
+                                                              const float* __restrict__ b1, const float* __restrict__ w2,
+                                                              const float* __restrict__ b2, float* __restrict__ s,
+                                                              float* __restrict__ mz, long hw, int c, int hid) {
+  __shared__ float4 red[8][MAXC / 4];
+  __shared__ float sm[MAXC], sz[HAT_CA_MAXHID];
   const int b = blockIdx.x, t = threadIdx.x;
-  chan_sum<false>(u, nullptr, hw, c, sm, red);
+  chan_sum<false, MAXC>(u, nullptr, hw, c, sm, red);
   if (t < c) {
     sm[t] = sm[t] / (float)hw;
     mz[(long)b * (c + hid) + t] = sm[t];
@@ -579,15 +583,16 @@ __global__ __launch_bounds__(256) void hat_combine_fwd_kernel(const float4* __re
 
 // per image: dsig[c] = cs sum_p g u, dl = dsig s (1 - s), dz = [z > 0] w2^T dl, dm = w1^T dz / hw.
 // scratch per image: [dl (c) | dz (hid) | dm / hw (c)]
-__global__ __launch_bounds__(256) void hat_ca_bwd_kernel(const float* __restrict__ g, const float* __restrict__ u,
-                                                         const float* __restrict__ s, const float* __restrict__ mz,
-                                                         const float* __restrict__ w1, const float* __restrict__ w2,
-                                                         float* __restrict__ scratch, float cs, long hw, int c, int hid) {
-  __shared__ float4 red[8][HAT_CA_MAXC / 4];
-  __shared__ float sd[HAT_CA_MAXC], sdl[HAT_CA_MAXC], sdz[HAT_CA_MAXHID];
+template <int MAXC>
+__global__ __launch_bounds__(2 * MAXC) void hat_ca_bwd_kernel(const float* __restrict__ g, const float* __restrict__ u,
+                                                              const float* __restrict__ s, const float* __restrict__ mz,
+                                                              const float* __restrict__ w1, const float* __restrict__ w2,
+                                                              float* __restrict__ scratch, float cs, long hw, int c, int hid) {
+  __shared__ float4 red[8][MAXC / 4];
+  __shared__ float sd[MAXC], sdl[MAXC], sdz[HAT_CA_MAXHID];
   const int b = blockIdx.x, t = threadIdx.x;
   const int row = 2 * c + hid;
-  chan_sum<true>(g, u, hw, c, sd, red);
+  chan_sum<true, MAXC>(g, u, hw, c, sd, red);
   if (t < c) {
     const float sv = s[(long)b * c + t];
     const float dl = (cs * sd[t]) * sv * (1.f - sv);
@@ -761,12 +766,20 @@ static int ca_check(const char* who, int n, long hw, int c, int hid) {
   return SRHIP_OK;
 }
 
+// the published widths: 128 < C <= 192
+static int ca_wide_check(const char* who, int n, long hw, int c, int hid) {
+  SRHIP_REQUIRE(n > 0 && hw > 0 && c % 4 == 0 && c > HAT_CA_MAXC && c <= HAT_CA_WIDE_MAXC && hid >= 1 && hid <= HAT_CA_MAXHID,
+                "%s: C %% 4 == 0, %d < C <= %d, 1 <= hidden <= %d (got %d, %d)", who, HAT_CA_MAXC, HAT_CA_WIDE_MAXC, HAT_CA_MAXHID, c,
+                hid);
+  return SRHIP_OK;
+}
+
 int srhip_hat_ca_fwd(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* mz, int n,
                      long hw, int c, int hid, void* stream) {
   SRHIP_REQUIRE(u && w1 && w2 && s && mz && aligned16(u), "hat_ca_fwd: bad arguments");
   int rc = ca_check("hat_ca_fwd", n, hw, c, hid);
   if (rc) return rc;
-  hat_ca_fwd_kernel<<<n, 256, 0, as_stream(stream)>>>(u, w1, b1, w2, b2, s, mz, hw, c, hid);
+  hat_ca_fwd_kernel<HAT_CA_MAXC><<<n, 256, 0, as_stream(stream)>>>(u, w1, b1, w2, b2, s, mz, hw, c, hid);
   return check_launch("hat_ca_fwd");
 }
 
@@ -784,28 +797,35 @@ int srhip_hat_combine_fwd(const float* x, const float* a, const float* kb, const
 
 size_t srhip_hat_combine_bwd_workspace(int n, int c, int hid) { return (size_t)n * (2 * c + hid) * 4; }
 
-int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
-                          const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
-                          size_t workspace_bytes, float cs, int n, long hw, int c, int hid, void* stream) {
+}  // extern "C"
+
+template <bool WIDE>
+static int combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
+                       const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                       size_t workspace_bytes, float cs, int n, long hw, int c, int hid, void* stream) {
+  const char* who = WIDE ? "hatw_combine_bwd" : "hat_combine_bwd";
   SRHIP_REQUIRE(g && n > 0 && hw > 0 && c % 4 == 0 && c > 0 && aligned16(g) && (!da || aligned16(da)),
-                "hat_combine_bwd: bad arguments");
+                "%s: bad arguments", who);
   hipStream_t st = as_stream(stream);
   const long per = hw * c / 4, quads = per * n;
   if (!du) {
     hat_combine_bwd_kernel<<<ew_grid(quads), 256, 0, st>>>(reinterpret_cast<const float4*>(g), kb, nullptr, nullptr,
                                                            reinterpret_cast<float4*>(da), nullptr, cs, quads, per, c / 4, 0, 0);
-    return check_launch("hat_combine_bwd");
+    return check_launch(who);
   }
-  int rc = ca_check("hat_combine_bwd", n, hw, c, hid);
+  int rc = WIDE ? ca_wide_check(who, n, hw, c, hid) : ca_check(who, n, hw, c, hid);
   if (rc) return rc;
   SRHIP_REQUIRE(u && s && mz && w1 && w2 && aligned16(u) && aligned16(s) && aligned16(du) && aligned16(workspace),
-                "hat_combine_bwd: bad channel-attention arguments");
+                "%s: bad channel-attention arguments", who);
   if (!workspace || workspace_bytes < srhip_hat_combine_bwd_workspace(n, c, hid)) {
-    set_error("hat_combine_bwd: workspace %zu bytes < required %zu", workspace_bytes, srhip_hat_combine_bwd_workspace(n, c, hid));
+    set_error("%s: workspace %zu bytes < required %zu", who, workspace_bytes, srhip_hat_combine_bwd_workspace(n, c, hid));
     return SRHIP_ERR_WORKSPACE;
   }
   float* scratch = static_cast<float*>(workspace);
-  hat_ca_bwd_kernel<<<n, 256, 0, st>>>(g, u, s, mz, w1, w2, scratch, cs, hw, c, hid);
+  if (WIDE)
+    hat_ca_bwd_kernel<HAT_CA_WIDE_MAXC><<<n, 2 * HAT_CA_WIDE_MAXC, 0, st>>>(g, u, s, mz, w1, w2, scratch, cs, hw, c, hid);
+  else
+    hat_ca_bwd_kernel<HAT_CA_MAXC><<<n, 256, 0, st>>>(g, u, s, mz, w1, w2, scratch, cs, hw, c, hid);
   rc = check_launch("hat_ca_bwd");
   if (rc) return rc;
   const int nw = 2 * c * hid + c + hid;
@@ -815,7 +835,32 @@ int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const
   hat_combine_bwd_kernel<<<ew_grid(quads), 256, 0, st>>>(reinterpret_cast<const float4*>(g), kb, reinterpret_cast<const float4*>(s),
                                                          scratch, reinterpret_cast<float4*>(da), reinterpret_cast<float4*>(du), cs,
                                                          quads, per, c / 4, 2 * c + hid, c + hid);
-  return check_launch("hat_combine_bwd");
+  return check_launch(who);
+}
+
+extern "C" {
+
+int srhip_hat_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
+                          const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                          size_t workspace_bytes, float cs, int n, long hw, int c, int hid, void* stream) {
+  return combine_bwd<false>(g, kb, u, s, mz, w1, w2, da, du, dw1, db1, dw2, db2, workspace, workspace_bytes, cs, n, hw, c, hid,
+                            stream);
+}
+
+int srhip_hatw_ca_fwd(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, float* s, float* mz, int n,
+                      long hw, int c, int hid, void* stream) {
+  SRHIP_REQUIRE(u && w1 && w2 && s && mz && aligned16(u), "hatw_ca_fwd: NULL or misaligned tensor");
+  int rc = ca_wide_check("hatw_ca_fwd", n, hw, c, hid);
+  if (rc) return rc;
+  hat_ca_fwd_kernel<HAT_CA_WIDE_MAXC><<<n, 2 * HAT_CA_WIDE_MAXC, 0, as_stream(stream)>>>(u, w1, b1, w2, b2, s, mz, hw, c, hid);
+  return check_launch("hatw_ca_fwd");
+}
+
+int srhip_hatw_combine_bwd(const float* g, const float* kb, const float* u, const float* s, const float* mz, const float* w1,
+                           const float* w2, float* da, float* du, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                           size_t workspace_bytes, float cs, int n, long hw, int c, int hid, void* stream) {
+  return combine_bwd<true>(g, kb, u, s, mz, w1, w2, da, du, dw1, db1, dw2, db2, workspace, workspace_bytes, cs, n, hw, c, hid,
+                           stream);
 }
 
 }  // extern "C"

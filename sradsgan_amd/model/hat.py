@@ -22,6 +22,16 @@ from .dssr import _Shuffle
 from .layers import HipConv2d
 
 HEAD_DIM = 16
+# The two families the kernels serve, nothing in between: the reference's (embed_dim 96, six heads of 16 channels, window 8 or 9;
+# srhip_hat_*) and the published HAT / HAT-L / HAT-S (embed_dim 180 or 144, six heads of 30 or 24, window 16, overlap 0.5; srhip_hatw_*)
+WIDE_DIMS = (144, 180)
+WIDE_WINDOW = 16
+FAMILIES = ('embed_dim 96 with six heads of 16 channels and window_size 8 or 9 (the reference), or embed_dim 144 / 180 with six '
+            'heads of 24 / 30 channels, window_size 16 and overlap_ratio 0.5 (HAT-S, HAT, HAT-L)')
+
+
+def _family_ok(dim, window_size):
+    return (dim == 96 and window_size in (8, 9)) or (dim in WIDE_DIMS and window_size == WIDE_WINDOW)
 
 
 def to_2tuple(x):
@@ -44,12 +54,12 @@ class HipLinear(nn.Linear):
 
 
 class HipLayerNorm(nn.LayerNorm):
-    """nn.LayerNorm(96) over the channels of every pixel."""
+    """nn.LayerNorm(C) over the channels of every pixel, C = 96, 144 or 180."""
 
     def __init__(self, normalized_shape, eps=1e-5, elementwise_affine=True):
         super().__init__(normalized_shape, eps=eps, elementwise_affine=elementwise_affine)
-        _refuse(tuple(self.normalized_shape) != (96,) or eps != 1e-5 or not elementwise_affine,
-                'LayerNorm(96, eps=1e-5) with its affine parameters only')
+        _refuse(tuple(self.normalized_shape) not in ((96,),) + tuple((c,) for c in WIDE_DIMS) or eps != 1e-5
+                or not elementwise_affine, 'LayerNorm(96 / 144 / 180, eps=1e-5) with its affine parameters only')
 
     def forward(self, x):
         return ops.layer_norm(x, self.weight, self.bias)
@@ -82,8 +92,9 @@ class ChannelAttention(nn.Module):
     def __init__(self, num_feat, squeeze_factor=16):
         super().__init__()
         hidden = num_feat // squeeze_factor
-        _refuse(not 1 <= hidden <= 16 or num_feat % 4 or num_feat > 128,
-                'channel attention with C %% 4 == 0, C <= 128 and 1..16 hidden units, got %d / %d' % (num_feat, hidden))
+        _refuse(not 1 <= hidden <= 16 or num_feat % 4 or (num_feat > 128 and num_feat not in WIDE_DIMS),
+                'channel attention with C %% 4 == 0, C <= 128 or C = 144 / 180, and 1..16 hidden units, got %d / %d'
+                % (num_feat, hidden))
         self.attention = nn.Sequential(nn.AdaptiveAvgPool2d(1), HipConv2d(num_feat, hidden, 1, padding=0), nn.ReLU(inplace=True),
                                        HipConv2d(hidden, num_feat, 1, padding=0), nn.Sigmoid())
 
@@ -147,7 +158,8 @@ class WindowAttention(nn.Module):
 
     def forward(self, xn, shift=0):
         ws = self.window_size[0]
-        _refuse(self.window_size[1] != ws or ws not in (8, 9), 'windows of 8 or 9, got %s' % (self.window_size,))
+        _refuse(self.window_size[1] != ws or not _family_ok(self.dim, ws) or self.num_heads != 6,
+                'got dim %d, %d heads, window %s; supported: %s' % (self.dim, self.num_heads, self.window_size, FAMILIES))
         o = ops.window_attention(self.qkv(xn), self.relative_position_bias_table, ops.HAT_SA, ws, shift)
         return self.proj(o)
 
@@ -233,7 +245,8 @@ class OCAB(nn.Module):
         self.mlp = Mlp(in_features=dim, hidden_features=mlp_hidden_dim, act_layer=nn.GELU)
 
     def forward(self, x, x_size=None, rpi=None):
-        _refuse(self.window_size not in (8, 9), 'windows of 8 or 9, got %d' % self.window_size)
+        _refuse(not _family_ok(self.dim, self.window_size) or self.num_heads != 6,
+                'got dim %d, %d heads, window %d; supported: %s' % (self.dim, self.num_heads, self.window_size, FAMILIES))
         o = ops.window_attention(self.qkv(self.norm1(x)), self.relative_position_bias_table, ops.HAT_OCA, self.window_size)
         x = self.proj(o, residual=x)
         return self.mlp(self.norm2(x), residual=x)
@@ -353,9 +366,11 @@ class Upsample(nn.Sequential):
 
 
 class GeneratorResNet(nn.Module):
-    """hat.py:617-875 with the same arguments and defaults.  The HIP path runs embed_dim 96 with heads of 16 channels and windows of
-    8 or 9; ape, dropout rates above 0, upsampler != 'pixelshuffle', resi_connection != '1conv', use_checkpoint and in_chans != 3
-    raise NotImplementedError."""
+    """hat.py:617-875 with the same arguments and defaults.  The HIP path runs two families: embed_dim 96 with six heads of 16
+    channels and windows of 8 or 9 (what the reference's trainer builds), and the published HAT / HAT-L (embed_dim 180) and HAT-S
+    (embed_dim 144) with six heads, window 16 and overlap_ratio 0.5, at any depths, compress_ratio, squeeze_factor (1..16 hidden
+    units) and mlp_ratio; any other width / heads / window combination, ape, dropout rates above 0, upsampler != 'pixelshuffle',
+    resi_connection != '1conv', use_checkpoint and in_chans != 3 raise NotImplementedError."""
 
     def __init__(self, img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=(6, 6, 6, 6, 6, 6), num_heads=(6, 6, 6, 6, 6, 6),
                  window_size=9, compress_ratio=3, squeeze_factor=30, conv_scale=0.01, overlap_ratio=0.5, mlp_ratio=4., qkv_bias=True,
@@ -369,10 +384,10 @@ class GeneratorResNet(nn.Module):
         _refuse(resi_connection != '1conv', "resi_connection='1conv' only")
         _refuse(use_checkpoint, 'use_checkpoint')
         _refuse(in_chans != 3, 'in_chans=3 only')
-        _refuse(embed_dim != 96 or any(embed_dim // h != HEAD_DIM or embed_dim % h for h in num_heads),
-                'embed_dim 96 with heads of %d channels' % HEAD_DIM)
-        _refuse(window_size not in (8, 9), 'window_size 8 or 9')
-        _refuse(qk_scale not in (None, HEAD_DIM ** -0.5), 'qk_scale None (head_dim ** -0.5)')
+        _refuse(not _family_ok(embed_dim, window_size) or any(h != 6 for h in num_heads)
+                or (embed_dim in WIDE_DIMS and int(window_size * overlap_ratio) != window_size // 2),
+                'got embed_dim %d, num_heads %s, window_size %s; supported: %s' % (embed_dim, tuple(num_heads), window_size, FAMILIES))
+        _refuse(qk_scale not in (None, (embed_dim // 6) ** -0.5), 'qk_scale None (head_dim ** -0.5)')
         self.window_size = window_size
         self.shift_size = window_size // 2
         self.overlap_ratio = overlap_ratio
@@ -399,7 +414,7 @@ class GeneratorResNet(nn.Module):
         self.patch_unembed = PatchUnEmbed(img_size=img_size, patch_size=patch_size, in_chans=embed_dim, embed_dim=embed_dim,
                                           norm_layer=norm_layer if self.patch_norm else None)
         self.pos_drop = nn.Dropout(p=drop_rate)
-        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths), device='cpu')]   # (host values also under a meta default device)
         self.layers = nn.ModuleList()
         for i_layer in range(self.num_layers):
             self.layers.append(RHAG(

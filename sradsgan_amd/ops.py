@@ -3773,6 +3773,16 @@ def channel_attention_bias_prelu(x, w1, b1, slope, w2, b2):
 
 
 HAT_SA, HAT_OCA = 0, 1
+HAT_WIDE_DIMS = (144, 180)          # the published widths (csrc/hat_wide.hip: srhip_hatw_*); 96 is the reference's (srhip_hat_*)
+
+
+def _hat_family(c, what):
+    """False: the reference's family (C = 96, srhip_hat_*); True: the published one (C = 144 / 180, srhip_hatw_*)."""
+    if c == 96:
+        return False
+    if c in HAT_WIDE_DIMS:
+        return True
+    raise ValueError('%s: %d channels belong to neither HAT family (96; %s)' % (what, c, ' / '.join(map(str, HAT_WIDE_DIMS))))
 
 
 class _Linear(Function):
@@ -3812,16 +3822,22 @@ def _hat_tokens(x, c, what):
 
 
 class _LayerNorm(Function):
-    """nn.LayerNorm(96) over the channels of every pixel (eps 1e-5)."""
+    """nn.LayerNorm(C) over the channels of every pixel (eps 1e-5), C = 96 or a published width."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        x = _hat_tokens(x, 96, 'layer_norm')
-        tokens = x.numel() // 96
+        c = weight.numel()
+        wide = _hat_family(c, 'layer_norm')
+        x = _hat_tokens(x, c, 'layer_norm')
+        tokens = x.numel() // c
         y = torch.empty_like(x, memory_format=CL)
         stats = torch.empty(2, tokens, device=x.device, dtype=torch.float32)
-        _hip.check(_hip.lib().srhip_hat_ln_fwd(_p(x), _p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(y),
-                                               _p(stats[0]), _p(stats[1]), tokens, _stream()), 'hat_ln_fwd')
+        if wide:
+            _hip.check(_hip.lib().srhip_hatw_ln_fwd(_p(x), _p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(y),
+                                                    _p(stats[0]), _p(stats[1]), tokens, c, _stream()), 'hatw_ln_fwd')
+        else:
+            _hip.check(_hip.lib().srhip_hat_ln_fwd(_p(x), _p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(y),
+                                                   _p(stats[0]), _p(stats[1]), tokens, _stream()), 'hat_ln_fwd')
         ctx.save_for_backward(x, weight, stats)
         return y
 
@@ -3830,12 +3846,18 @@ class _LayerNorm(Function):
     def backward(ctx, dy):
         x, weight, stats = ctx.saved_tensors
         dy = nhwc(dy)
-        tokens = x.numel() // 96
+        c = weight.numel()
+        tokens = x.numel() // c
         lib = _hip.lib()
         dx = torch.empty_like(x, memory_format=CL)
-        part = torch.empty(lib.srhip_hat_ln_parts(tokens) * 192, device=x.device, dtype=torch.float32)
         dg = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
         db = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
+        if c != 96:
+            part = torch.empty(lib.srhip_hatw_ln_parts(tokens) * 2 * c, device=x.device, dtype=torch.float32)
+            _hip.check(lib.srhip_hatw_ln_bwd(_p(dy), _p(x), _p(weight.detach().contiguous()), _p(stats[0]), _p(stats[1]), None, _p(dx),
+                                             _p(part), _p(dg), _p(db), tokens, c, _stream()), 'hatw_ln_bwd')
+            return dx, dg, db
+        part = torch.empty(lib.srhip_hat_ln_parts(tokens) * 192, device=x.device, dtype=torch.float32)
         _hip.check(lib.srhip_hat_ln_bwd(_p(dy), _p(x), _p(weight.detach().contiguous()), _p(stats[0]), _p(stats[1]), None, _p(dx),
                                         _p(part), _p(dg), _p(db), tokens, _stream()), 'hat_ln_bwd')
         return dx, dg, db
@@ -3872,16 +3894,30 @@ def gelu(x):
 
 
 class _WindowAttention(Function):
-    """softmax(q k^T / 4 + table[rpi] [+ mask]) v per window and head, from the qkv Linear's output [n, 288, h, w]; the output
-    [n, 96, h, w] sits at the pixels' own positions (the reference's roll / partition / unfold / reverse are addressing)."""
+    """softmax(q k^T D^-0.5 + table[rpi] [+ mask]) v per window and head, from the qkv Linear's output [n, 3C, h, w]; the output
+    [n, C, h, w] sits at the pixels' own positions (the reference's roll / partition / unfold / reverse are addressing).  The table's
+    second dimension is the head count; C = 96 goes to srhip_hat_attn_*, the published widths to srhip_hatw_attn_*."""
 
     @staticmethod
     def forward(ctx, qkv, table, kind, ws, shift):
-        qkv = _hat_tokens(qkv, 288, 'window_attention')
+        _require_gpu(qkv, 'window_attention')
+        if qkv.dim() != 4 or qkv.shape[1] % 3:
+            raise ValueError('window_attention: expected [n, 3C, h, w], got %s' % (tuple(qkv.shape),))
+        c, heads = qkv.shape[1] // 3, table.shape[1]
+        wide = _hat_family(c, 'window_attention')
+        qkv = _hat_tokens(qkv, 3 * c, 'window_attention')
         n, _, h, w = qkv.shape
+        tab = table.detach().contiguous()
+        if wide:
+            out = empty_nhwc(n, c, h, w, qkv)
+            lse = torch.empty(n * h * w * heads, device=qkv.device, dtype=torch.float32)
+            _hip.check(_hip.lib().srhip_hatw_attn_fwd(_p(qkv), _p(tab), _p(out), _p(lse), kind, n, h, w, c, heads, ws, shift,
+                                                      _stream()), 'hatw_attn_fwd')
+            ctx.save_for_backward(qkv, tab, out, lse)
+            ctx.cfg = (kind, ws, shift)
+            return out
         out = empty_nhwc(n, 96, h, w, qkv)
         lse = torch.empty(n * h * w * 6, device=qkv.device, dtype=torch.float32)
-        tab = table.detach().contiguous()
         _hip.check(_hip.lib().srhip_hat_attn_fwd(_p(qkv), _p(tab), _p(out), _p(lse), kind, n, h, w, ws, shift, _stream()),
                    'hat_attn_fwd')
         ctx.save_for_backward(qkv, tab, out, lse)
@@ -3898,6 +3934,13 @@ class _WindowAttention(Function):
         lib = _hip.lib()
         dqkv = torch.empty_like(qkv, memory_format=CL)
         dtab = torch.empty_like(tab)
+        c, heads = qkv.shape[1] // 3, tab.shape[1]
+        if c != 96:
+            nbytes = lib.srhip_hatw_attn_bwd_workspace(kind, n, h, w, c, heads, ws)
+            wsp = torch.empty((nbytes + 3) // 4, device=qkv.device, dtype=torch.float32)
+            _hip.check(lib.srhip_hatw_attn_bwd(_p(qkv), _p(tab), _p(out), _p(dout), _p(lse), _p(dqkv), _p(dtab), _p(wsp), nbytes, kind,
+                                               n, h, w, c, heads, ws, shift, _stream()), 'hatw_attn_bwd')
+            return dqkv, dtab, None, None, None
         nbytes = lib.srhip_hat_attn_bwd_workspace(kind, n, h, w, ws)
         wsp = torch.empty((nbytes + 3) // 4, device=qkv.device, dtype=torch.float32)
         _hip.check(lib.srhip_hat_attn_bwd(_p(qkv), _p(tab), _p(out), _p(dout), _p(lse), _p(dqkv), _p(dtab), _p(wsp), nbytes, kind, n,
@@ -3929,9 +3972,9 @@ class _HabCombine(Function):
             mz = torch.empty(n, c + hid, device=x.device, dtype=torch.float32)
             if b1 is None or b2 is None:
                 raise ValueError('hab_combine: the channel attention has biases (nn.Conv2d default)')
-            _hip.check(lib.srhip_hat_ca_fwd(_p(u), _p(w1.detach().contiguous()), _p(b1.detach().contiguous()),
-                                            _p(w2.detach().contiguous()), _p(b2.detach().contiguous()), _p(s), _p(mz), n, h * w, c,
-                                            hid, _stream()), 'hat_ca_fwd')
+            ca_fwd = lib.srhip_hatw_ca_fwd if c in HAT_WIDE_DIMS else lib.srhip_hat_ca_fwd
+            _hip.check(ca_fwd(_p(u), _p(w1.detach().contiguous()), _p(b1.detach().contiguous()), _p(w2.detach().contiguous()),
+                              _p(b2.detach().contiguous()), _p(s), _p(mz), n, h * w, c, hid, _stream()), 'hat_ca_fwd')
         _hip.check(lib.srhip_hat_combine_fwd(_p(x), _p(a), _p(kb), _p(u), _p(s), _p(out), float(cs), n, h * w, c, _stream()),
                    'hat_combine_fwd')
         ctx.save_for_backward(u, w1, w2, kb, s, mz)
@@ -3956,9 +3999,10 @@ class _HabCombine(Function):
         dw2, db2 = torch.empty_like(w2), torch.empty(c, device=g.device, dtype=torch.float32)
         nbytes = lib.srhip_hat_combine_bwd_workspace(n, c, hid)
         wsp = torch.empty((nbytes + 3) // 4, device=g.device, dtype=torch.float32)
-        _hip.check(lib.srhip_hat_combine_bwd(_p(g), _p(kb), _p(u), _p(s), _p(mz), _p(w1.detach().contiguous()),
-                                             _p(w2.detach().contiguous()), _p(da), _p(du), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(wsp),
-                                             nbytes, ctx.cs, n, h * w, c, hid, _stream()), 'hat_combine_bwd')
+        combine_bwd = lib.srhip_hatw_combine_bwd if c in HAT_WIDE_DIMS else lib.srhip_hat_combine_bwd
+        _hip.check(combine_bwd(_p(g), _p(kb), _p(u), _p(s), _p(mz), _p(w1.detach().contiguous()), _p(w2.detach().contiguous()),
+                               _p(da), _p(du), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(wsp), nbytes, ctx.cs, n, h * w, c, hid,
+                               _stream()), 'hat_combine_bwd')
         return g, da, du, dw1, db1, dw2, db2, None, None
 
 
