@@ -990,6 +990,30 @@ int srhip_diff_q_sample(const float* x0, long ldx0, const float* noise, long ldn
                         const float* sqrt_ac, const float* sqrt_1mac, int steps, long n, long rows_per_sample, int ch,
                         unsigned long long seed, unsigned long long step, void* stream);
 
+/* ABI 14 (additive) -- the dihedral group on image batches (csrc/augment.hip; data.Augment, ensemble.py).  Exact permutations, no
+ * atomics, re-runs are bit-identical.
+ * Op encoding, the same in every call: op in 0..7, bit 0 = transpose (swap H and W), bit 1 = flip top-bottom, bit 2 = flip
+ *   left-right, applied in that order: y = fliplr^b2(flipud^b1(transpose^b0(x))).
+ *   srhip_augment_u8: in = uint8 [n][h][w][c] (c <= 4), params_dev = DEVICE int [n][4] = {y0, x0, op, 0}, out = uint8 [n][cs][cs][c],
+ *     4-byte aligned.  Sample k of out is op_k applied to the cs x cs crop of sample k at (y0_k, x0_k); a crop that leaves the source
+ *     or an op outside 0..7 (the device table cannot be checked on the host) yields a zero tile, never an out-of-bounds read.
+ *     With sigma > 0, Gaussian noise is added to the crop BEFORE the op, in double: byte' = trunc(clip((double)byte + sigma * z, 0, 255))
+ *     (numpy's clip(..).astype(uint8)), z = the fp32 tensor z [n][cs][cs][c] indexed in the un-rotated crop, or, with z == NULL and
+ *     drawn != 0, the value srhip_diff_randn(seed, step) writes for element ((k * cs + y) * cs + x) * c + ch.  sigma == 0 launches
+ *     the kernel without any noise code.  Whole dwords are stored, with scalar row heads and tails.
+ *   srhip_dihedral_f32: y = op(x) for a float tensor, logically x [n][c][h][w] and y [n][c][oh][ow] ((oh, ow) = (w, h) for a
+ *     transposing op), each given by four element strides {n, c, h, w} read on the HOST -- NCHW-dense and channels-last alike.
+ *     float4 per thread when c % 4 == 0, both channel strides are 1 and both sides are 16-byte aligned; scalar otherwise.
+ *   srhip_ensemble_merge_f32: views = HOST array of m <= 8 device pointers, view_strides = HOST long [m][4], ops = HOST int [m];
+ *     view k has the shape of op_k(out).  out[n][c][y][x] = (((v_0 + v_1) + v_2) + ... + v_{m-1}) * (1.0f / m) in fp32, in index
+ *     order, v_k read where op_k sends (y, x) (i.e. through the inverse of op_k); one pass, no workspace.                        */
+int srhip_augment_u8(const unsigned char* in, const int* params_dev, const float* z, unsigned char* out, int n, int h, int w, int c,
+                     int cs, double sigma, int drawn, unsigned long long seed, unsigned long long step, void* stream);
+int srhip_dihedral_f32(const float* x, const long* x_strides, float* y, const long* y_strides, int n, int c, int h, int w, int op,
+                       void* stream);
+int srhip_ensemble_merge_f32(const float* const* views, const long* view_strides, const int* ops, int m, float* out,
+                             const long* out_strides, int n, int c, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

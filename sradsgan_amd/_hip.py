@@ -241,6 +241,9 @@ SIGNATURES = {
     'srhip_diff_attn_bwd_workspace': (_sz, [_i, _i, _i]),
     'srhip_diff_attn_bwd': (_i, [_vp] * 6 + [_sz] + [_i] * 4 + [_vp]),
     'srhip_diff_q_sample': (_i, [_vp, _l] * 3 + [_vp] * 3 + [_i, _l, _l, _i, _u64, _u64, _vp]),
+    'srhip_augment_u8': (_i, [_vp] * 4 + [_i] * 5 + [ctypes.c_double, _i, _u64, _u64, _vp]),
+    'srhip_dihedral_f32': (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    'srhip_ensemble_merge_f32': (_i, [_vp, _vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp]),
 }
 
 _lib = None

@@ -322,18 +322,7 @@ __global__ void __launch_bounds__(64) diff_attn_kernel(const float* __restrict__
 // ---- sampler --------------------------------------------------------------------------------------------------------------- //
 // four standard normals of counter `group` (= element index / 4) under key (seed, step)
 __device__ __forceinline__ void diff_normal4(unsigned long long seed, unsigned long long step, unsigned long long group, float z[4]) {
-  const philox_words w = philox4x32_10((unsigned)group, (unsigned)(group >> 32), (unsigned)step, (unsigned)(step >> 32), (unsigned)seed,
-                                       (unsigned)(seed >> 32));
-  const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const float u1 = ((float)(u[2 * k] >> 9) + 0.5f) * 1.1920928955078125e-07f;       // (0, 1), 23 bits + 1/2: exact in fp32
-    const float u2 = ((float)(u[2 * k + 1] >> 9) + 0.5f) * 1.1920928955078125e-07f;
-    const float rad = sqrtf(-2.f * logf(u1));
-    const float th = 6.283185307179586f * u2;
-    z[2 * k] = rad * cosf(th);
-    z[2 * k + 1] = rad * sinf(th);
-  }
+  philox_normal4(seed, step, group, z);            // philox.h: shared with augment.hip, which must draw the same bits
 }
 
 // a thread owns the four consecutive elements of one Philox counter; element e = row * ch + channel

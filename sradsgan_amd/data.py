@@ -88,6 +88,126 @@ def training_batch(hr_u8, scale):
 
 
 # --------------------------------------------------------------------------------------------- #
+# training augmentation (Dataset.__getitem__, data/dataset.py:248-326): crop -> Gaussian noise -> rotation by 90 * {1, 2, 3}
+# degrees -> horizontal flip -> vertical flip, per BATCH of uint8 tiles in one gather kernel (csrc/augment.hip).
+#
+# One op encoding everywhere (include/sradsgan_hip.h): bit 0 transpose, bit 1 flip top-bottom, bit 2 flip left-right, applied
+# in that order.  Pillow's rotate(90 rv, expand=True) turns counter-clockwise: 90 = flipud(transpose), 180 = flipud(fliplr),
+# 270 = fliplr(transpose); the two flips that follow commute with each other and toggle their own bit.
+# --------------------------------------------------------------------------------------------- #
+
+_ROTATION_OPS = (0, 3, 6, 5)
+# (rv, fliplr, fliptb) -> op for Pillow's rotate(90 * rv, expand=True), then FLIP_LEFT_RIGHT, then FLIP_TOP_BOTTOM
+DIHEDRAL_OP = {(rv, lr, tb): _ROTATION_OPS[rv] ^ (lr << 2) ^ (tb << 1) for rv in range(4) for lr in (0, 1) for tb in (0, 1)}
+# op -> the op that undoes it: the flips are their own inverses, under a transpose they change places
+DIHEDRAL_INVERSE = (0, 1, 2, 5, 4, 3, 6, 7)
+
+
+def augment_u8(hr_u8, params_dev, cs, sigma=0.0, z=None, seed=0, step=0):
+    """hr_u8: [N, H, W, C] uint8 on the HIP device; params_dev: int32 [N, 4] = (y0, x0, op, 0) on the device.  Returns uint8
+    [N, cs, cs, C]: per sample the cs x cs crop at (y0, x0), with Gaussian noise when sigma > 0 -- trunc(clip(double(byte) +
+    sigma * z, 0, 255)), z the fp32 tensor `z` [N, cs, cs, C] or, when it is None, the Philox normals gdp_kernels.randn_rows(seed, step)
+    writes for the same elements -- and then the dihedral op.  Asynchronous on the current stream."""
+    _require_gpu_u8(hr_u8, 'augment_u8')
+    n, h, w, c = hr_u8.shape
+    cs, sigma = int(cs), float(sigma)
+    if cs > h or cs > w:
+        raise NotImplementedError('augment_u8: the %dx%d source is smaller than the %d crop (the reference pads it with black through '
+                                  'torchvision; not carried over)' % (h, w, cs))
+    if not (torch.is_tensor(params_dev) and params_dev.is_cuda and params_dev.dtype == torch.int32 and tuple(params_dev.shape) == (n, 4)):
+        raise TypeError('augment_u8: params must be an int32 [%d, 4] tensor on the device' % n)
+    if z is not None and not (z.is_cuda and z.dtype == torch.float32 and tuple(z.shape) == (n, cs, cs, c)):
+        raise TypeError('augment_u8: z must be a float32 [%d, %d, %d, %d] tensor on the device' % (n, cs, cs, c))
+    hr_u8, params_dev = hr_u8.contiguous(), params_dev.contiguous()
+    z = None if (z is None or sigma == 0.0) else z.contiguous()
+    out = torch.empty(n, cs, cs, c, device=hr_u8.device, dtype=torch.uint8)
+    _hip.check(_hip.lib().srhip_augment_u8(_p(hr_u8), _p(params_dev), None if z is None else _p(z), _p(out), n, h, w, c, cs, sigma,
+                                           int(z is None and sigma != 0.0), int(seed), int(step),
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'augment_u8')
+    return out
+
+
+class Augment:
+    """The reference's training augmentation (Dataset.__getitem__, dataset.py:273-306) for a batch of uint8 tiles of one common
+    source size: centre crop (torchvision's rule) or random crop to cs = calculate_valid_crop_size(crop_size, scale_factor),
+    Gaussian noise `noise=['Gaussain', sigma]` (the reference's spelling; 'Gaussian' is taken too), rotation by 90 * rv degrees
+    with rv uniform in {1, 2, 3} (never 0, as there), horizontal and vertical flips with p = 1/2 each.  The draws come from a
+    torch.Generator seeded with seed + rank, so data-parallel ranks differ; the noise from Philox keyed by (seed + rank, call
+    number).  The reference draws from Python's and numpy's global generators instead: the distribution is the same, the
+    stream is not.  `last_params` (host int32 [N, 4] = y0, x0, op, 0) and `last_step` record the latest call.
+
+    Not carried over, each a NotImplementedError: random_scale (the reference's ratio guards always resize the whole image
+    to crop_size x crop_size, so it squashes the image instead of jittering the scale), 'Poisson' noise (it calls .numpy() on
+    a PIL image and raises there too), is_gray, and a source smaller than the crop."""
+
+    def __init__(self, crop_size, scale_factor, random_crop=False, rotate=False, fliplr=False, fliptb=False, noise=None, seed=None,
+                 rank=0, random_scale=False, is_gray=False):
+        if random_scale:
+            raise NotImplementedError('Augment: random_scale is not carried over: in the reference its ratio guards always resize the '
+                                      'whole image to crop_size x crop_size (dataset.py:260-271), a squash, not a scale jitter')
+        if is_gray:
+            raise NotImplementedError('Augment: RGB tiles only (is_gray=False is what the trainers pass)')
+        self.sigma = 0.0
+        if noise is not None:
+            kind, value = noise[0], noise[1]
+            if kind == 'Poisson':
+                raise NotImplementedError("Augment: 'Poisson' noise is not carried over: the reference calls .numpy() on a PIL image "
+                                          'there (dataset.py:287) and raises')
+            if kind not in ('Gaussain', 'Gaussian'):
+                raise ValueError("Augment: noise must be None or ['Gaussain', sigma], got %r" % (noise,))
+            self.sigma = float(value)
+            if not self.sigma >= 0.0:
+                raise ValueError('Augment: the noise sigma must be non-negative, got %r' % (value,))
+        self.scale_factor = int(scale_factor)
+        self.crop_size = calculate_valid_crop_size(int(crop_size), self.scale_factor)
+        if self.crop_size <= 0:
+            raise ValueError('Augment: crop_size %r leaves no valid crop at scale %d' % (crop_size, self.scale_factor))
+        self.random_crop, self.rotate, self.fliplr, self.fliptb = bool(random_crop), bool(rotate), bool(fliplr), bool(fliptb)
+        self.generator = torch.Generator()
+        self.seed = (self.generator.seed() if seed is None else int(seed) + int(rank)) & 0x7fffffffffffffff
+        self.generator.manual_seed(self.seed)
+        self.step = 0                                    # Philox step of the next call
+        self.last_params, self.last_step = None, None
+
+    def draw(self, n, H, W):
+        """Host int32 [n, 4] = (y0, x0, op, 0) for n tiles of an H x W source."""
+        cs, g = self.crop_size, self.generator
+        if cs > H or cs > W:
+            raise NotImplementedError('Augment: the %dx%d source is smaller than the %d crop (the reference pads it with black through '
+                                      'torchvision; not carried over)' % (H, W, cs))
+        out = torch.zeros(n, 4, dtype=torch.int32)
+        if self.random_crop:
+            out[:, 0] = torch.randint(0, H - cs + 1, (n,), generator=g)
+            out[:, 1] = torch.randint(0, W - cs + 1, (n,), generator=g)
+        else:                                            # torchvision's center_crop
+            out[:, 0], out[:, 1] = int(round((H - cs) / 2.0)), int(round((W - cs) / 2.0))
+        rv = torch.randint(1, 4, (n,), generator=g) if self.rotate else torch.zeros(n, dtype=torch.int64)
+        lr = torch.randint(0, 2, (n,), generator=g) if self.fliplr else torch.zeros(n, dtype=torch.int64)
+        tb = torch.randint(0, 2, (n,), generator=g) if self.fliptb else torch.zeros(n, dtype=torch.int64)
+        out[:, 2] = torch.tensor([DIHEDRAL_OP[k] for k in zip(rv.tolist(), lr.tolist(), tb.tolist())], dtype=torch.int32)
+        return out
+
+    def __call__(self, hr_u8, z=None):
+        """hr_u8: [N, H, W, C] uint8 on the device -> uint8 [N, cs, cs, C].  The table goes up through pinned memory on the
+        current stream and the kernel follows it: nothing here waits for the device.  z: supplied noise instead of the drawn one."""
+        _require_gpu_u8(hr_u8, 'Augment')
+        n, h, w, _ = hr_u8.shape
+        params = self.draw(n, h, w)
+        staged = torch.empty((n, 4), dtype=torch.int32, pin_memory=True)       # torch's pinned pool: re-used once the copy has run
+        staged.copy_(params)
+        out = augment_u8(hr_u8, staged.to(hr_u8.device, non_blocking=True), self.crop_size, self.sigma, z, self.seed, self.step)
+        self.last_params, self.last_step = params, self.step
+        self.step += 1
+        return out
+
+
+def augmented_training_batch(hr_u8, scale, augment):
+    """training_batch of the augmented tiles: exactly Dataset.__getitem__ (dataset.py:248-326) -- its HR Resize is the identity
+    at the crop size."""
+    return training_batch(augment(hr_u8), scale)
+
+
+# --------------------------------------------------------------------------------------------- #
 # host side of the input pipeline: file listing + decode (data/dataset.py:88-101, 386-441) and the loader
 # (sradsgan.py:643-656: shuffle, drop_last).  Decode stays on the host (Pillow, worker threads); everything after the
 # uint8 HR tile -- LR / bicubic synthesis, to_tensor -- is `training_batch` / `test_batch` on the device.

@@ -313,13 +313,16 @@ class DDPM:
                 raise RuntimeError('gdp_train.DDPM: loading the checkpoint detached the parameters from the arena')
 
 
-def training_batch(hr_u8, lr_size):
+def training_batch(hr_u8, lr_size, augment=None):
     """uint8 HR tiles [N, H, W, 3] on the device -> {'HR', 'SR', 'LR'} float32 in [-1, 1] as prepare_data.py (Pillow bicubic down to
-    lr_size, then back up to H x W) and LRHR_dataset.py (to_tensor * 2 - 1) make them."""
+    lr_size, then back up to H x W) and LRHR_dataset.py (to_tensor * 2 - 1) make them.  augment: a data.Augment applied to the tiles
+    first (crop to its crop size, noise, rotation, flips); None = the tiles as they are."""
     if not torch.is_tensor(hr_u8) or hr_u8.dtype != torch.uint8 or hr_u8.dim() != 4:
         raise TypeError('training_batch expects a [N, H, W, 3] uint8 tensor')
     if not hr_u8.is_cuda:
         raise RuntimeError('training_batch: runs on the MI355X HIP path only (got a %s tensor); there is no CPU fallback' % hr_u8.device.type)
+    if augment is not None:
+        hr_u8 = augment(hr_u8)
     _, h, w, _ = hr_u8.shape
     lr = sdata.resize_u8(hr_u8, lr_size, lr_size)
     sr = sdata.resize_u8(lr, h, w)

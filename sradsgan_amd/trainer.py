@@ -31,6 +31,7 @@ from . import dp
 from . import lpips as slpips
 from . import ops
 from . import validate as sval
+from .ensemble import SelfEnsemble
 from .model import Discriminator, FeatureExtractor, GeneratorResNet, PatchDiscriminator, ResGroup
 from .model.discriminators import NORM_TYPES
 from .model.spectral import SpectralPatchDiscriminator, spectral_init_
@@ -44,7 +45,11 @@ def default_args(**overrides):
              num_epochs=100, save_epochs=1, batch_size=16, test_batch_size=1, save_dir='Result', lr=0.0002, b1=0.9, b2=0.999,
              gpu_mode=True, test_crop_size=216, n_cpu=16, hr_height=216, hr_width=216, sample_interval=1000, clip_value=0.01,
              lambda_gp=10, gp=True, penalty_type='LS', grad_penalty_Lp_norm='L2', relativeGan=False, loss_Lp_norm='L1',
-             weight_content=1e-2, weight_gan=1e-3, max_train_samples=40000, is_train=True)
+             weight_content=1e-2, weight_gan=1e-3, max_train_samples=40000, is_train=True,
+             # not in main_sradsgan.py: the augmentation Dataset.__getitem__ offers (data.Augment; all off = no Augment is built)
+             # and x8 geometric self-ensemble at validation (ensemble.SelfEnsemble)
+             augment_random_crop=False, augment_rotate=False, augment_fliplr=False, augment_fliptb=False, augment_noise=None,
+             augment_seed=None, self_ensemble=False)
     d.update(overrides)
     return argparse.Namespace(**d)
 
@@ -81,6 +86,18 @@ def attention_ablation(args):
     if not isinstance(opts['addconv'], bool):
         raise ValueError('args.addconv must be a bool, got %r' % (opts['addconv'],))
     return opts
+
+
+def training_augment(args, rank=0):
+    """The data.Augment that `args.augment_*` ask for -- the crop / noise / rotation / flips of Dataset.__getitem__ (dataset.py:273-306)
+    for uint8 training tiles -- or None when every switch is off (absent fields are off): then nothing is built and the trainer's
+    batches are the un-augmented ones."""
+    flags = dict(random_crop=bool(getattr(args, 'augment_random_crop', False)), rotate=bool(getattr(args, 'augment_rotate', False)),
+                 fliplr=bool(getattr(args, 'augment_fliplr', False)), fliptb=bool(getattr(args, 'augment_fliptb', False)),
+                 noise=getattr(args, 'augment_noise', None))
+    if not any(flags.values()):
+        return None
+    return sdata.Augment(args.crop_size, args.scale_factor, seed=getattr(args, 'augment_seed', None), rank=rank, **flags)
 
 
 class SRADSGAN(object):
@@ -125,6 +142,7 @@ class SRADSGAN(object):
         self.pretrained_generator = getattr(args, 'pretrained_generator', None)      # chain training, see _build
         self.pretrained_discriminator = getattr(args, 'pretrained_discriminator', None)
         self.train_loader, self.test_loader = train_loader, test_loader
+        self.self_ensemble = bool(getattr(args, 'self_ensemble', False))            # validate / mfeNew_validate report the "+" numbers
         self.lpips = None
         self.lpips_alexnet = getattr(args, 'lpips_alexnet', None)                    # state-dict paths, see set_lpips
         self.lpips_lin = getattr(args, 'lpips_lin', None)
@@ -135,6 +153,7 @@ class SRADSGAN(object):
         # logs, validation results and with them every rollback decision are rank 0's
         self.rank, self.world = dp.rank_world()
         self.device = torch.device('cuda', torch.cuda.current_device())
+        self.augment = training_augment(args, self.rank)                            # None unless an augmentation switch is on
         self.generator = self.discriminator = self.feature_extractor = None
         self.step = None
         self.log_dict = OrderedDict()
@@ -209,6 +228,8 @@ class SRADSGAN(object):
         if isinstance(item, (tuple, list)) and len(item) == 2 and torch.is_tensor(item[0]) and item[0].dtype == torch.uint8:
             item = item[0]
         if torch.is_tensor(item) and item.dtype == torch.uint8:
+            if not test and getattr(self, 'augment', None) is not None:              # training tiles only, never the test set
+                return sdata.augmented_training_batch(item.to(self.device), self.scale_factor, self.augment)
             make = sdata.test_batch if test else sdata.training_batch
             return make(item.to(self.device), self.scale_factor)
         lr, hr, bc = item[0], item[1], item[2]
@@ -318,7 +339,9 @@ class SRADSGAN(object):
         if lpips is not None:
             sums['bicubic_lpips'] = sums[label + '_lpips'] = 0.0
         img_num = 0
-        was_training = generator.training
+        was_training, inner = generator.training, generator
+        if getattr(self, 'self_ensemble', False):                                                # the "+" protocol: 8 views, merged
+            generator = SelfEnsemble(inner)
         generator.eval()                                                                         # :1288
         start = time.time()
         for item in loader:
@@ -328,7 +351,7 @@ class SRADSGAN(object):
             for k in metrics:
                 sums['bicubic_' + k] += float(out['bicubic'][k].sum())
                 sums[label + '_' + k] += float(out['sr'][k].sum())
-        generator.train(was_training)
+        inner.train(was_training)
         if totals is not None:                                                                   # running sums over classes
             totals['num'] = totals.get('num', 0) + img_num
             for k, v in sums.items():
@@ -411,8 +434,11 @@ class SRADSGAN(object):
         u8 = torch.from_numpy(np.asarray(img.crop((left, top, left + c, top + c)), dtype=np.uint8).copy())
         u8 = u8.unsqueeze(0).contiguous().to(self.device)                                        # [1,c,c,3] uint8
         x = sdata.to_tensor(u8)
+        gen = self.generator
+        if getattr(self, 'self_ensemble', False):
+            gen = SelfEnsemble(gen)
         with torch.no_grad():
-            sr = self.generator(x)
+            sr = gen(x)
         bc_u8 = sdata.resize_u8(u8, c * self.scale_factor, c * self.scale_factor, 'bicubic')[0]  # [H,W,3]
         sr_u8 = (sr[0] * 255.0).clamp(0, 255).to(torch.uint8).permute(1, 2, 0)                   # save_img1
         os.makedirs(self.save_dir, exist_ok=True)
