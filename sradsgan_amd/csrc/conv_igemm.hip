@@ -412,107 +412,197 @@ __global__ __launch_bounds__(256) void igemm_wgrad_kernel(const float* __restric
 
 // ---- forward of 3x3 stride-1 pad-1 convs with <= 3 input channels (discriminator / VGG / generator head) ---------- //
 // K = 9*Cin <= 27 pads to 32 = sixteen 32x32x2 fp32 MFMA steps; the whole weight matrix (32 x 64) lives in registers.
-// A block takes one image row: the three input rows (zero halo) are staged in LDS, a wave owns 32 consecutive output
-// pixels x 64 channels, gathers its A values from LDS and stores 128-byte channel runs.  Write-bound by design.
+// A block takes `rows_per_block` consecutive image rows in chunks of `rows_chunk`: the chunk's rows_chunk + 2 input rows are staged in
+// LDS ONCE (zero outside the tensor; a filter row that would cross an image's top or bottom edge reads zero instead -- the staged
+// neighbour row there belongs to the next image), then the chunk's 32-pixel groups are dealt round-robin to the four waves
+// (4 rows x 7 groups at W = 216: seven each, where a row at a time left the fourth wave idle every second round).  Blocks do not
+// double-buffer: several share a CU and one's staging runs under the others' MFMAs.
+// The WEIGHTS are the MFMA's A operand and the pixels its B operand, so a lane ends up with ONE pixel (ow0 + l31) and 2 x 16 channels
+// ((i & 3) + 8 * (i >> 2) + 4 * half of each accumulator) in runs of four: the epilogue is float4 arithmetic on the lane's own pixel,
+// the tile goes through a wave-private LDS buffer (32 channels at a time) and leaves as 16-byte stores, eight lanes per 128-byte run.
+// (With the pixels as the A operand a lane is a channel: 32 dword stores and, for the record, 32 ballots or 64 lane reads per group.)
+// The products, their order over k and the epilogue arithmetic are those of that transposed form: y and the record are bit for bit the same.
 // MASK (cout == 64 only; `rec` = one 64-bit word per output pixel, bit c = (y[pixel][c] > 0), NaN and both zeros give 0):
-//   1: the epilogue also WRITES the record of its output -- per pixel the ballots of the two accumulator halves, one 256-byte store
-//      per wave and 32 pixels -- so that the backward passes of the fused LeakyReLU read 1 bit per element instead of y;
-//   2: the epilogue READS a record and multiplies by the mask, v = bit ? v : v * slope (the activation's backward applied to this
-//      conv's output: the second-order pass of the gradient penalty, d_dy = mask * conv(ddx, w)), no other activation.
-template <int MASK>
-__global__ __launch_bounds__(256) void headconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ packed,
-                                                            const float* __restrict__ bias, float* __restrict__ y,
-                                                            unsigned long long* __restrict__ rec,
-                                                            int N, int H, int W, int cin, int cout, int ldx, int ldy,
-                                                            int ldw, float slope, int flags, int rows_per_block) {
-  extern __shared__ float xs[];                      // [3][W + 2][cin]
+//   1: the epilogue also WRITES the record of its output -- a lane collects the bits of its own pixel's channels, the two half-waves
+//      exchange theirs, one 256-byte store per wave and 32 pixels -- so that the backward passes of the fused LeakyReLU read 1 bit
+//      per element instead of y;
+//   2: the epilogue READS a record (each lane its own pixel's word) and multiplies by the mask, v = bit ? v : v * slope (the
+//      activation's backward applied to this conv's output: the second-order pass of the gradient penalty,
+//      d_dy = mask * conv(ddx, w)), no other activation.
+constexpr int HEAD_TLD = 36;                             // floats per pixel row of the epilogue tile: 32 channels + 4 (conflict-free b128 writes)
+constexpr int HEAD_XS_PAD = 4;                           // floats past the staged rows that a dropped read may touch
+constexpr int HEAD_FIXED_LDS = (4 * 32 * HEAD_TLD + 64 + HEAD_XS_PAD) * (int)sizeof(float);   // four wave tiles, the bias, the pad
+
+// rows a block stages at a time (<= rows_per_block, all of it within 64 KB of LDS; head_conv_shape bounds three rows by 32 KB)
+static int headconv_rows_chunk(int w, int cin, int rows_per_block, size_t* lds_bytes) {
+  const size_t row = (size_t)(w + 2) * cin * sizeof(float);
+  const int fit = (int)((64 * 1024 - HEAD_FIXED_LDS) / row) - 2;
+  const int rc = rows_per_block < fit ? rows_per_block : fit;
+  *lds_bytes = HEAD_FIXED_LDS + (size_t)(rc + 2) * row;
+  return rc;
+}
+
+template <int MASK, int CIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MASK == 0 ? 4 : 3))) void headconv_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ packed, const float* __restrict__ bias, float* __restrict__ y,
+    unsigned long long* __restrict__ rec, int N, int H, int W, int cout, int ldx, int ldy, int ldw, float slope, int flags,
+    int rows_per_block, int rows_chunk) {
+  extern __shared__ __attribute__((aligned(16))) float head_lds[];
+  constexpr int KTOT = 9 * CIN;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, half = lane >> 5;
   const int co0 = blockIdx.y * 64;
-  const int ktot = 9 * cin;
-  const int rowlen = (W + 2) * cin;
-  int koff[16];
-  float bw0[16], bw1[16];
+  const int rowlen = (W + 2) * CIN;
+  float* tile = head_lds + wave * (32 * HEAD_TLD);   // [32 pixels][HEAD_TLD], this wave's alone
+  float* bs = head_lds + 4 * 32 * HEAD_TLD;          // [64] bias of channels co0 .. co0 + 63 (zero without one)
+  float* xs = bs + 64;                               // [rows_chunk + 2][W + 2][CIN] (+ HEAD_XS_PAD)
+  float bw0[16], bw1[16];                            // step s_ of a lane multiplies column k = 2 s_ + half
 #pragma unroll
   for (int s_ = 0; s_ < 16; ++s_) {
     const int k = 2 * s_ + half;
-    koff[s_] = -1;
     bw0[s_] = bw1[s_] = 0.f;
-    if (k < ktot) {
-      const int tap = k / cin, ci = k - tap * cin;
-      const int kh = tap / 3, kw = tap - kh * 3;
-      koff[s_] = kh * rowlen + kw * cin + ci;
+    if (k < KTOT) {
       if (co0 + l31 < cout) bw0[s_] = packed[(size_t)k * ldw + co0 + l31];
       if (co0 + 32 + l31 < cout) bw1[s_] = packed[(size_t)k * ldw + co0 + 32 + l31];
     }
   }
-  float b0 = 0.f, b1 = 0.f;
-  if (flags & SRHIP_EPI_BIAS) {
-    if (co0 + l31 < cout) b0 = bias[co0 + l31];
-    if (co0 + 32 + l31 < cout) b1 = bias[co0 + 32 + l31];
-  }
-  // a block walks `rows_per_block` consecutive image rows: the 32 weight loads per lane and the tap offsets above are paid once
-  for (int r = blockIdx.x * rows_per_block; r < min((int)(blockIdx.x + 1) * rows_per_block, N * H); ++r) {
-  const int n = r / H, oh = r - n * H;
-  __syncthreads();                                   // the previous row's gathers are done
-  for (int e = tid; e < 3 * rowlen; e += 256) {
-    const int kh = e / rowlen, rem = e - kh * rowlen;
-    const int col = rem / cin, ci = rem - col * cin;
-    const int ih = oh + kh - 1, iw = col - 1;
-    xs[e] = (ih >= 0 && ih < H && iw >= 0 && iw < W) ? x[((size_t)(n * H + ih) * W + iw) * ldx + ci] : 0.f;
-  }
-  __syncthreads();
-  for (int ow0 = wave * 32; ow0 < W; ow0 += 128) {
-    const int p = min(ow0 + l31, W - 1);             // lanes past the row end compute a duplicate, never stored
-    f32x16 acc0, acc1;
+  if (tid < 64) bs[tid] = ((flags & SRHIP_EPI_BIAS) && co0 + tid < cout) ? bias[co0 + tid] : 0.f;   // (visible after the first barrier below)
+  // 16-byte stores need whole, aligned channel quads; anything else (a narrow cout, an odd row stride) leaves the tile as dwords
+  const bool vec = co0 + 64 <= cout && (ldy & 3) == 0 && (reinterpret_cast<size_t>(y) & 15) == 0;
+  const int groups_per_row = (W + 31) >> 5;
+  const int rowskip = rowlen - 3 * CIN;
+  const int rows_total = N * H;
+  const int r_begin = blockIdx.x * rows_per_block, r_end = min(r_begin + rows_per_block, rows_total);
+  // the 32 weight loads per lane above are paid once per block
+  for (int r0 = r_begin; r0 < r_end; r0 += rows_chunk) {
+    const int nr = min(rows_chunk, r_end - r0);
+    __syncthreads();                                 // the previous chunk's gathers are done
+    // staged row s = tensor row r0 - 1 + s.  Eight loads per thread are in flight before the first LDS write: one element per trip
+    // exposed the memory latency once per 256 elements.
+    const unsigned total = (unsigned)(nr + 2) * rowlen;
+    for (unsigned e0 = tid; e0 < total; e0 += 256 * 8) {
+      float v[8];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
-    // the record word of pixel ow0 + l31, as two dwords (both half-waves hold the same 32 words): MASK 2 loads it here, one coalesced
-    // 256-byte read per wave whose latency the gathers and MFMAs below cover; MASK 1 collects it from the ballots of the epilogue
-    unsigned wlo = 0u, whi = 0u;
-    if (MASK == 2 && ow0 + l31 < W) {
-      const unsigned long long m = rec[(size_t)r * W + ow0 + l31];
-      wlo = (unsigned)m;
-      whi = (unsigned)(m >> 32);
-    }
+      for (int u = 0; u < 8; ++u) {
+        const unsigned e = e0 + 256 * u;
+        const unsigned s = e / (unsigned)rowlen, j = e - s * rowlen;
+        const unsigned col = j / CIN, ci = j - col * CIN;
+        const int gr = r0 - 1 + (int)s, iw = (int)col - 1;
+        v[u] = (e < total && gr >= 0 && gr < rows_total && iw >= 0 && iw < W) ? x[((size_t)gr * W + iw) * ldx + ci] : 0.f;
+      }
 #pragma unroll
-    for (int s_ = 0; s_ < 16; ++s_) {
-      const float a = koff[s_] >= 0 ? xs[p * cin + koff[s_]] : 0.f;
-      acc0 = mfma32(a, bw0[s_], acc0);
-      acc1 = mfma32(a, bw1[s_], acc1);
+      for (int u = 0; u < 8; ++u)
+        if (e0 + 256 * u < total) xs[e0 + 256 * u] = v[u];
     }
+    __syncthreads();
+    for (int gi = wave; gi < nr * groups_per_row; gi += 4) {     // (wave-uniform: scalar arithmetic)
+      const int lr = gi / groups_per_row, ow0 = (gi - lr * groups_per_row) * 32;
+      const int r = r0 + lr, oh = r % H;
+      const bool top = oh == 0, bot = oh == H - 1;
+      const int p = min(ow0 + l31, W - 1);           // lanes past the row end compute a duplicate, never stored
+      // column k = (kh, kw, ci) of pixel p lies at xs[(lr + kh) * rowlen + (p + kw) * CIN + ci] = xp[2 s_ + kh * rowskip] (3 CIN columns per filter row)
+      const float* xp = xs + lr * rowlen + p * CIN + half;
+      // the record word of this lane's pixel as two dwords, moved down by 4 * half so that bit (i & 3) + 8 * (i >> 2) is the bit of the
+      // lane's accumulator i: MASK 2 loads it here, one coalesced 256-byte read per half-wave whose latency the gathers and MFMAs below
+      // cover; MASK 1 collects it in the epilogue
+      unsigned wrec[2] = {0u, 0u};
+      if (MASK == 2 && ow0 + l31 < W) {
+        const unsigned long long m = rec[(size_t)r * W + ow0 + l31];
+        wrec[0] = (unsigned)m >> (4 * half);
+        wrec[1] = (unsigned)(m >> 32) >> (4 * half);
+      }
+      // all reads first, unconditionally (a select, not a branch, drops what a step must not see): the filter row of a step is a
+      // compile-time constant except where the two half-waves' columns straddle two rows.  A filter row across the image's top or
+      // bottom edge reads zero (the staged row there is the neighbouring image's); steps past the last column still run, on zeros.
+      float a[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int px = (i & 3) + 8 * (i >> 2);          // accumulator i: pixel ow0 + px in lanes 0-31, ow0 + px + 4 in lanes 32-63
-      const int ow = ow0 + px + 4 * half;
-      float v0 = acc0[i] + b0, v1 = acc1[i] + b1;
-      if (MASK == 2) {                                // (all lanes are active here: the lane reads below need no exec care)
-        const unsigned lo = half ? (unsigned)__builtin_amdgcn_readlane((int)wlo, px + 4) : (unsigned)__builtin_amdgcn_readlane((int)wlo, px);
-        const unsigned hi = half ? (unsigned)__builtin_amdgcn_readlane((int)whi, px + 4) : (unsigned)__builtin_amdgcn_readlane((int)whi, px);
-        v0 = ((lo >> l31) & 1u) ? v0 : v0 * slope;
-        v1 = ((hi >> l31) & 1u) ? v1 : v1 * slope;
-      } else if (flags & SRHIP_EPI_LRELU) {
-        v0 = v0 > 0.f ? v0 : v0 * slope;
-        v1 = v1 > 0.f ? v1 : v1 * slope;
+      for (int s_ = 0; s_ < 16; ++s_) {
+        const bool ok0 = 2 * s_ < KTOT, ok1 = 2 * s_ + 1 < KTOT;
+        const int kh0 = 2 * s_ / (3 * CIN), kh1 = (2 * s_ + 1) / (3 * CIN);
+        a[s_] = 0.f;
+        if (ok0) {
+          // (KTOT is odd: in its last step the upper half-wave has no column; it reads the lower one's neighbour, at most
+          // one float past the staged rows -- HEAD_XS_PAD -- and drops it)
+          const int kh = (ok1 && half) ? kh1 : kh0;
+          const float t = xp[2 * s_ + kh * rowskip];
+          const bool dead = (!ok1 && half) || (kh == 0 && top) || (kh == 2 && bot);
+          a[s_] = dead ? 0.f : t;
+        }
       }
-      if (MASK == 1) {
-        // lanes 0-31 hold channels 0-31 (v0) and 32-63 (v1) of one pixel, lanes 32-63 those of the pixel four columns on: the low
-        // dwords of the two ballots are the first pixel's word, the high dwords the second's; lane px (px + 4) keeps it
-        const unsigned long long q0 = __ballot(v0 > 0.f), q1 = __ballot(v1 > 0.f);
-        wlo = l31 == px ? (unsigned)q0 : (l31 == px + 4 ? (unsigned)(q0 >> 32) : wlo);
-        whi = l31 == px ? (unsigned)q1 : (l31 == px + 4 ? (unsigned)(q1 >> 32) : whi);
+      f32x16 acc[2];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[0][i] = acc[1][i] = 0.f;
+#pragma unroll
+      for (int s_ = 0; s_ < 16; ++s_) {
+        acc[0] = mfma32(bw0[s_], a[s_], acc[0]);
+        acc[1] = mfma32(bw1[s_], a[s_], acc[1]);
       }
-      if (ow < W) {
-        float* o = y + ((size_t)r * W + ow) * ldy + co0 + l31;
-        if (co0 + l31 < cout) o[0] = v0;
-        if (co0 + 32 + l31 < cout) o[32] = v1;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {               // channels co0 + 32 * hh .. + 31
+        unsigned bits = 0u;
+        float4 bqs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bqs[j] = *reinterpret_cast<const float4*>(bs + 32 * hh + 8 * j + 4 * half);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                // accumulators 4 j .. 4 j + 3: channels 8 j + 4 * half .. + 3
+          const float4 bq = bqs[j];
+          float v[4] = {acc[hh][4 * j] + bq.x, acc[hh][4 * j + 1] + bq.y, acc[hh][4 * j + 2] + bq.z, acc[hh][4 * j + 3] + bq.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (MASK == 2)
+              v[q] = ((wrec[hh] >> (8 * j + q)) & 1u) ? v[q] : v[q] * slope;
+            else if (flags & SRHIP_EPI_LRELU)
+              v[q] = v[q] > 0.f ? v[q] : v[q] * slope;
+            if (MASK == 1) bits |= v[q] > 0.f ? 1u << (8 * j + q) : 0u;
+          }
+          *reinterpret_cast<float4*>(tile + l31 * HEAD_TLD + 8 * j + 4 * half) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        if (MASK == 1) {                             // the other half-wave holds the pixel's other 16 channels (all lanes are active here)
+          bits <<= 4 * half;
+          wrec[hh] = bits | (unsigned)__shfl_xor((int)bits, 32);
+        }
+        // the tile is written and read by this wave alone and LDS serves a wave's accesses in order: only the compiler must keep the order
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float* yg = y + ((size_t)r * W + ow0) * ldy + co0 + 32 * hh;     // (uniform; the lanes add 32-bit offsets: 32 pixels of one row)
+        if (vec) {                                   // 8 pixels x 128 bytes per instruction; the four reads together, then the stores
+          const int px0 = lane >> 3, cq = lane & 7;
+          const float* tq = tile + px0 * HEAD_TLD + 4 * cq;
+          const float4 o0 = *reinterpret_cast<const float4*>(tq), o1 = *reinterpret_cast<const float4*>(tq + 8 * HEAD_TLD);
+          const float4 o2 = *reinterpret_cast<const float4*>(tq + 16 * HEAD_TLD), o3 = *reinterpret_cast<const float4*>(tq + 24 * HEAD_TLD);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+          __builtin_amdgcn_wave_barrier();           // (the next half overwrites the tile)
+          float* yq = yg + (unsigned)(px0 * ldy + 4 * cq);
+          if (ow0 + px0 < W) *reinterpret_cast<float4*>(yq) = o0;
+          if (ow0 + px0 + 8 < W) *reinterpret_cast<float4*>(yq + (unsigned)(8 * ldy)) = o1;
+          if (ow0 + px0 + 16 < W) *reinterpret_cast<float4*>(yq + (unsigned)(16 * ldy)) = o2;
+          if (ow0 + px0 + 24 < W) *reinterpret_cast<float4*>(yq + (unsigned)(24 * ldy)) = o3;
+        } else {
+#pragma unroll 2
+          for (int t = 0; t < 16; ++t) {             // 2 pixels x 128 bytes per instruction
+            const int px = 2 * t + half;
+            const float o = tile[px * HEAD_TLD + l31];
+            if (ow0 + px < W && co0 + 32 * hh + l31 < cout) yg[(unsigned)(px * ldy + l31)] = o;
+          }
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+        }
       }
+      if (MASK == 1 && lane < 32 && ow0 + lane < W)  // one coalesced store of the group's <= 32 words
+        rec[(size_t)r * W + ow0 + lane] = ((unsigned long long)wrec[1] << 32) | wrec[0];
     }
-    if (MASK == 1 && lane < 32 && ow0 + lane < W)     // one coalesced store of the group's <= 32 words
-      rec[(size_t)r * W + ow0 + lane] = ((unsigned long long)whi << 32) | wlo;
   }
-  }
+}
+
+// cin is 1, 2 or 3 (head_conv_shape)
+template <int MASK>
+static void launch_headconv(dim3 grid, size_t lds, hipStream_t st, int cin, const float* x, const float* packed, const float* bias, float* y,
+                            unsigned long long* rec, int n, int h, int w, int cout, int ldx, int ldy, int ldw, float slope, int flags,
+                            int rows_per_block, int rows_chunk) {
+  auto kernel = cin == 1 ? headconv_fwd_kernel<MASK, 1> : (cin == 2 ? headconv_fwd_kernel<MASK, 2> : headconv_fwd_kernel<MASK, 3>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, x, packed, bias, y, rec, n, h, w, cout, ldx, ldy, ldw, slope, flags, rows_per_block,
+                     rows_chunk);
 }
 
 // ---- weight gradient of 3x3 stride-1 pad-1 convs with <= 3 input channels (discriminator / VGG head, 3 -> 64) ---- //
@@ -559,35 +649,67 @@ __global__ __launch_bounds__(256) void wgrad_smallcin_kernel(const float* __rest
   for (int r = r_begin; r < r_end; ++r) {
     const int n = r / H, oh = r - n * H;
     __syncthreads();
-    for (int e = tid; e < 3 * rowlen; e += 256) {
-      const int kh = e / rowlen, rem = e - kh * rowlen;
-      const int col = rem / cin, ci = rem - col * cin;
-      const int ih = oh + kh - 1, iw = col - 1;
-      xs[e] = (ih >= 0 && ih < H && iw >= 0 && iw < W) ? x[((size_t)(n * H + ih) * W + iw) * ldx + ci] : 0.f;
+    // eight loads per thread in flight before the first LDS write (the three rows of W = 216 are one trip): an element per trip paid
+    // the memory latency eight times per image row
+    for (int e0 = tid; e0 < 3 * rowlen; e0 += 256 * 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = e0 + 256 * u;
+        const int kh = e / rowlen, rem = e - kh * rowlen;
+        const int col = rem / cin, ci = rem - col * cin;
+        const int ih = oh + kh - 1, iw = col - 1;
+        v[u] = (e < 3 * rowlen && ih >= 0 && ih < H && iw >= 0 && iw < W) ? x[((size_t)(n * H + ih) * W + iw) * ldx + ci] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (e0 + 256 * u < 3 * rowlen) xs[e0 + 256 * u] = v[u];
     }
     __syncthreads();
     const float* drow = dy + (size_t)r * W * ldy + co0 + l31;
     const float* yrow = (!BITS && ymask) ? ymask + (size_t)r * W * ldy + co0 + l31 : nullptr;
     const unsigned long long* brow = BITS ? ybits + (size_t)r * W : nullptr;
-#pragma unroll 4
-    for (int ow = 2 * wave; ow < W; ow += 8) {       // this wave's pixel pairs (ow, ow + 1)
-      const int p = ow + half;
-      const bool pok = p < W;
-      float d0 = (pok && c0ok) ? drow[(size_t)p * ldy] : 0.f;
-      float d1 = (pok && c1ok) ? drow[(size_t)p * ldy + 32] : 0.f;
-      if (BITS) {
-        const unsigned long long m = pok ? brow[p] : ~0ull;
-        if (!((m >> l31) & 1ull)) d0 *= slope;
-        if (!((m >> (32 + l31)) & 1ull)) d1 *= slope;
-      } else if (yrow != nullptr) {
-        if (pok && c0ok && !(yrow[(size_t)p * ldy] > 0.f)) d0 *= slope;
-        if (pok && c1ok && !(yrow[(size_t)p * ldy + 32] > 0.f)) d1 *= slope;
+    // this wave's pixel pairs (ow, ow + 1), ow = 2 * wave + 8 i, four at a time: every global load of the four first, then their
+    // arithmetic in the order of the pairs (a pair per trip waited for its own loads: 27 exposed latencies per row at W = 216)
+    constexpr int PF = 4;
+    for (int owb = 2 * wave; owb < W; owb += 8 * PF) {
+      float d0[PF], d1[PF], y0[PF], y1[PF];
+      unsigned long long m[PF];
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int p = owb + 8 * u + half;
+        const bool pok = p < W;
+        d0[u] = (pok && c0ok) ? drow[(size_t)p * ldy] : 0.f;
+        d1[u] = (pok && c1ok) ? drow[(size_t)p * ldy + 32] : 0.f;
+        m[u] = ~0ull;
+        y0[u] = y1[u] = 1.f;
+        if (BITS) {
+          if (pok) m[u] = brow[p];
+        } else if (yrow != nullptr) {
+          if (pok && c0ok) y0[u] = yrow[(size_t)p * ldy];
+          if (pok && c1ok) y1[u] = yrow[(size_t)p * ldy + 32];
+        }
       }
-      const float b = (pok && koff >= 0) ? xs[p * cin + koff] : 0.f;
-      bs0 += d0;
-      bs1 += d1;
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, b, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, b, acc1, 0, 0, 0);
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        if (owb + 8 * u < W) {                         // (wave-uniform)
+          const int p = owb + 8 * u + half;
+          const bool pok = p < W;
+          float e0 = d0[u], e1 = d1[u];
+          if (BITS) {
+            if (!((m[u] >> l31) & 1ull)) e0 *= slope;
+            if (!((m[u] >> (32 + l31)) & 1ull)) e1 *= slope;
+          } else if (yrow != nullptr) {
+            if (!(y0[u] > 0.f)) e0 *= slope;
+            if (!(y1[u] > 0.f)) e1 *= slope;
+          }
+          const float b = (pok && koff >= 0) ? xs[p * cin + koff] : 0.f;
+          bs0 += e0;
+          bs1 += e1;
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(e0, b, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(e1, b, acc1, 0, 0, 0);
+        }
+      }
     }
   }
   // sum the four waves' tiles through LDS, then one thread per (channel, column)
@@ -886,8 +1008,10 @@ int legacy_conv2d_fwd(const float* x, const float* packed, const float* bias, co
   g.M = (int)M; g.slope = slope; g.flags = flags; g.accumulate = 0;
   if (head_conv_shape(n, h, w, cin, kh, kw, stride, pad) && !(flags & ~(SRHIP_EPI_BIAS | SRHIP_EPI_LRELU))) {
     const int rpb = g_headconv_rows > 0 ? g_headconv_rows : 1;
-    hipLaunchKernelGGL(headconv_fwd_kernel<0>, dim3(cdiv((long)n * h, rpb), cdiv(cout, 64)), dim3(256), (size_t)3 * (w + 2) * cin * sizeof(float),
-                       as_stream(stream), x, packed, bias, y, (unsigned long long*)nullptr, n, h, w, cin, cout, ldx, ldy, g.ldw, slope, flags, rpb);
+    size_t lds = 0;
+    const int rchunk = headconv_rows_chunk(w, cin, rpb, &lds);
+    launch_headconv<0>(dim3(cdiv((long)n * h, rpb), cdiv(cout, 64)), lds, as_stream(stream), cin, x, packed, bias, y, nullptr, n, h, w, cout, ldx,
+                       ldy, g.ldw, slope, flags, rpb, rchunk);
     return check_launch("headconv_fwd");
   }
   return run_fprop(x, packed, bias, residual, rowscale, y, g, as_stream(stream));
@@ -911,14 +1035,15 @@ int legacy_headconv_fwd_mask(const float* x, const float* packed, const float* b
                 "conv2d_fwd_head_mask: mask_out goes with bias + LeakyReLU, mask_in with a plain epilogue");
   const int rpb = g_headconv_rows > 0 ? g_headconv_rows : 1;
   const dim3 grid(cdiv((long)n * h, rpb), 1);
-  const size_t lds = (size_t)3 * (w + 2) * cin * sizeof(float);
+  size_t lds = 0;
+  const int rchunk = headconv_rows_chunk(w, cin, rpb, &lds);
   const int ldw = legacy_packed_ld(cout);
   if (rec_out)
-    hipLaunchKernelGGL(headconv_fwd_kernel<1>, grid, dim3(256), lds, as_stream(stream), x, packed, bias, y, static_cast<unsigned long long*>(rec_out),
-                       n, h, w, cin, cout, ldx, ldy, ldw, slope, flags, rpb);
+    launch_headconv<1>(grid, lds, as_stream(stream), cin, x, packed, bias, y, static_cast<unsigned long long*>(rec_out), n, h, w, cout, ldx, ldy, ldw,
+                       slope, flags, rpb, rchunk);
   else
-    hipLaunchKernelGGL(headconv_fwd_kernel<2>, grid, dim3(256), lds, as_stream(stream), x, packed, bias, y,
-                       static_cast<unsigned long long*>(const_cast<void*>(rec_in)), n, h, w, cin, cout, ldx, ldy, ldw, slope, flags, rpb);
+    launch_headconv<2>(grid, lds, as_stream(stream), cin, x, packed, bias, y, static_cast<unsigned long long*>(const_cast<void*>(rec_in)), n, h, w,
+                       cout, ldx, ldy, ldw, slope, flags, rpb, rchunk);
   return check_launch("headconv_fwd_mask");
 }
 
