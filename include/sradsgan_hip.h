@@ -461,6 +461,9 @@ int srhip_prelu_slope_reduce(const float* partials, int nparts, float* da, int a
 /* ABI 14 -- AMSSRN's non-local attention on image quadrants (Nonlocal_CA, amssrn.py:93-165) and the gamma residual (:326-328).
  *   srhip_nl_quad_fwd : per quadrant of the split at h / 2, w / 2, y = softmax(theta^T phi) g; theta, phi, g, y dense NHWC tensors of
  *                       8 channels, [n, h, w, 8]; ml [n h w, 2] receives the row maximum and row sum of every query (for the backward).
+ *                       A NaN logit makes the row's y and row sum NaN, as torch's softmax; the saved maximum alone is not torch's
+ *                       amax there: it is the maximum of the row's logits that are not NaN (-inf when all are), and is only ever
+ *                       read together with the row sum.
  *   srhip_nl_quad_bwd : dtheta, dphi, dg from dy (same layout); dd [n h w] is scratch (dy . y per query).  Exact fp32, no atomics.
  *   srhip_gamma_res_fwd: out = a + gamma * b (gamma: one device float), dense, count % 4 == 0.
  *   srhip_gamma_res_bwd: db = gamma * g (db may be NULL) and srhip_gamma_parts() fixed-order partials of sum(g * b) (reduce with
@@ -793,6 +796,7 @@ int srhip_gn_bwd_bwd(const float* u, const float* dy, const float* x, const floa
 
 /* ---- validation metrics (mfeNew_validate / validate, sradsgan.py:1314-1325; utils/utils.py:923-962):
  *      images quantised like ToPILImage (mul(255).byte(): truncate + wrap, no clamp), NHWC floats in.
+ * A byte cannot carry a NaN: a NaN element is quantised to byte 0.
  * quant_sse: partial uint64 [n][srhip_metric_blocks()][2] = {sum (a_u8-b_u8)^2, sum b_u8} (exact);
  * ssim_u8 (scikit-image 0.15 compare_ssim, multichannel, 7x7 uniform window): partial double
  * [n][srhip_metric_blocks()] = sums of the SSIM index over interior pixels and channels (a = test, b = truth). */
@@ -829,7 +833,11 @@ int srhip_lpips_finish(const double* partial, const long* tap_pixels, int ntaps,
  * p,g,m,v: [n] arenas (n % 4 == 0, 16-byte aligned); g is multiplied by grad_scale first (1/world
  * for the data-parallel mean).  state: float[4] on the device {step, lr/(1-b1^step),
  * sqrt(1-b2^step), -}; the call advances it on the device, so it is hipGraph-capturable.
- * Arithmetic order follows torch.optim.Adam (eps added after sqrt(v)/sqrt(bias_correction2)).     */
+ * Arithmetic order follows torch.optim.Adam (eps added after sqrt(v)/sqrt(bias_correction2)).
+ * The clip is torch's clamp_, which keeps a NaN: a NaN gradient leaves m, v and p of that element
+ * NaN; a +inf gradient leaves m = v = +inf and p = NaN (inf / inf), the next finite gradient turns
+ * m NaN too and v stays +inf; a NaN weight stays NaN.  All with or without the clip, as
+ * torch.optim.Adam + clamp_ does; the float4 lane-mates of such an element are unaffected.        */
 int srhip_adam_step(float* p, const float* g, float* m, float* v, float* state, long n, float lr, float b1,
                     float b2, float eps, float grad_scale, float clip, void* stream);
 
@@ -912,7 +920,9 @@ int srhip_sn_backward_batched(const void* entries_dev, int count, const float* o
  *   (max-subtracted, no clipping; 0 for a label outside [0, c)), loss_sum[0] = their sum in fp64 in a fixed order, and, unless
  *   dlogits is null, dlogits = (softmax - onehot) * scale.
  * srhip_cls_confusion: arg[r] = the first index of the row's maximum -> pred[r] (may be null) and ++table[labels[r]][arg[r]]
- *   (int32 [c][c], may be null; the caller zeroes it, so several calls accumulate; labels outside [0, c) are not counted).     */
+ *   (int32 [c][c], may be null; the caller zeroes it, so several calls accumulate; labels outside [0, c) are not counted).
+ *   A NaN logit counts as the row's maximum (the first one wins), as in torch.argmax; srhip_cls_softmax_ce_fwd_bwd gives such a
+ *   row a NaN loss, NaN dlogits and a NaN loss_sum.                                                                             */
 size_t srhip_cls_channel_sums_workspace(int n, int h, int w);
 int srhip_cls_channel_sums(const unsigned char* img, long long* sums, void* workspace, size_t workspace_bytes, int n, int h, int w,
                            int c, void* stream);
@@ -942,7 +952,9 @@ int srhip_cls_confusion(const float* logits, const int* labels, int* pred, int* 
  *     Box-Muller on the four words; written with row stride ldo.  The bits do not depend on the launch shape.
  *   srhip_diff_sampler_step: out = c1 * clamp(x0, -1, 1) + c2 * xt + (t_nonzero ? exp(0.5 * logvar) * noise : 0) over rows x ch, every
  *     tensor with its own row stride; out may be xt.  noise == NULL draws srhip_diff_randn(seed, step)'s values in the kernel.
- *   srhip_diff_quant_u8: out[rows][ch] = uint8(rint((clamp(x, lo, hi) - lo) / (hi - lo) * 255)), round half to even.                     */
+ *     The clamp is torch's clamp_: x0 = +-inf counts as +-1, a NaN in x0 (or xt, or noise) stays NaN in out at that element only.
+ *   srhip_diff_quant_u8: out[rows][ch] = uint8(rint((clamp(x, lo, hi) - lo) / (hi - lo) * 255)), round half to even.  A byte cannot
+ *     carry a NaN: a NaN element is written as byte 0.                                                                                */
 size_t srhip_diff_gn_workspace(long n, long p);
 int srhip_diff_gn_fwd(const float* x, long ldx, const float* gamma, const float* beta, const float* scale, const float* shift, long ldmod,
                       float* y, long ldy, void* workspace, size_t workspace_bytes, long n, long p, int c, float eps, int silu,

@@ -252,7 +252,7 @@ __global__ void cls_confusion_kernel(const float* __restrict__ logits, const int
   float best = z[0];
   int arg = 0;
   for (int j = 1; j < c; ++j)
-    if (z[j] > best) {                                    // strict: the first maximum wins
+    if (pool_takes(z[j], best)) {                         // strict: the first maximum wins; a NaN logit is the maximum, as in torch.argmax
       best = z[j];
       arg = j;
     }

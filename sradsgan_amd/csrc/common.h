@@ -53,7 +53,13 @@ __device__ __forceinline__ unsigned pair_swap(unsigned v) {
 
 // max-pool comparisons propagate NaN like ATen's (adaptive_max_pool2d / max(dim)): a NaN beats every number, the first
 // NaN wins among NaNs -- a NaN activation must surface in the loss, not be masked by an attention gate (cbam.hip: the
-// discriminator's pair; attn_tail.hip: the generator's 48 CLAM / SLAM pools)
+// discriminator's pair; attn_tail.hip: the generator's 48 CLAM / SLAM pools).
+// The same holds for every clamp, clip, ReLU and norm over values that reach a loss, a weight or an image: fmaxf / fminf return
+// the OTHER operand when one is NaN and `d > 0.f ? d : 0.f` turns a NaN into 0, so these are written as comparisons a NaN fails --
+// ReLU `d < 0.f ? 0.f : d`, clamp `q < lo ? lo : (q > hi ? hi : q)`, running maximum `a > q || a != a` -- as ATen's relu, clamp_ and
+// max(dim) behave (losses.hip: the penalty's Linf norm and hinge; optim.hip: the weight clip; diffusion.hip: the sampler's clamp).
+// A soft-max may take its row maximum with fmaxf: expf(NaN - m) still poisons the row sum.  Only a byte output cannot carry a NaN;
+// the quantisers write 0 there and say so in include/sradsgan_hip.h.
 __device__ __forceinline__ bool pool_takes(float v, float mx) { return v > mx || (v != v && mx == mx); }
 __device__ __forceinline__ bool pool_merge_takes(float om, int oi, float mx, int idx) {
   const bool on = om != om, mn = mx != mx;

@@ -353,7 +353,8 @@ __global__ void diff_sampler_kernel(const float* __restrict__ x0, long ldx0, con
     if (e >= total) break;
     const long row = e / ch;
     const int cc = (int)(e % ch);
-    const float pred = fminf(fmaxf(x0[row * ldx0 + cc], -1.f), 1.f);
+    const float xp = x0[row * ldx0 + cc];
+    const float pred = xp < -1.f ? -1.f : (xp > 1.f ? 1.f : xp);   // clamp_ that keeps a NaN prediction NaN (fminf / fmaxf would return -1)
     float v = c1 * pred + c2 * xt[row * ldxt + cc];
     if (noise) v += sigma * noise[row * ldn + cc];
     else if (drawn) v += sigma * z[k];

@@ -189,7 +189,10 @@ __device__ __forceinline__ float gp_pixel_norm(const float* __restrict__ g, long
     const float v = g[p * c + j];
     if (NORM == GP_L2) q += v * v;
     else if (NORM == GP_L1) q += fabsf(v);
-    else q = fmaxf(q, fabsf(v));
+    else {
+      const float a = fabsf(v);
+      q = (a > q || a != a) ? a : q;               // torch.max(dim): a NaN channel makes the norm NaN (fmaxf would drop it)
+    }
   }
   return NORM == GP_L2 ? sqrtf(q) : q;
 }
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(256) void gp_opt_partial_kernel(const float* __rest
   float s = 0.f;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
     const float d = gp_pixel_norm<NORM>(g, p, c) - 1.f;
-    s += PEN == GP_LS ? d * d : (d > 0.f ? d : 0.f);
+    s += PEN == GP_LS ? d * d : (d < 0.f ? 0.f : d);   // ReLU that lets a NaN norm through like ATen's
   }
   s = block_sum_256(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;

@@ -9,6 +9,8 @@
 
 namespace srhip {
 
+// A NaN becomes byte 0 (include/sradsgan_hip.h promises it): fmaxf drops the NaN operand and returns -2.0e9f, and 2e9 is a multiple of
+// 256 -- a clamp constant that is not would change that byte.
 __device__ inline int quant_u8(float x) {
   float v = x * 255.f;
   v = fminf(fmaxf(v, -2.0e9f), 2.0e9f);

@@ -22,7 +22,7 @@ __device__ inline float adam_one(float& p, float g, float& m, float& v, float b1
   v = v * b2 + (1.f - b2) * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
   float denom = sqrtf(v) / bc2_sqrt + eps;
   float q = p - step_size * (m / denom);        // param.addcdiv_(exp_avg, denom, value=-step_size)
-  if (clip > 0.f) q = fminf(fmaxf(q, -clip), clip);
+  if (clip > 0.f) q = q < -clip ? -clip : (q > clip ? clip : q);   // clamp_ that keeps a NaN weight NaN (fminf / fmaxf would return -clip)
   p = q;
   return q;
 }

@@ -226,8 +226,10 @@ def sample(sd, cond, noise, betas, cfg, prefix='denoise_fn.', keep=False):
 
 
 def quantize(x):
-    """tensor2img(min_max=(-1, 1)) on [..., C] float32 rows: numpy's round is half to even."""
-    v = np.clip(np.asarray(x, dtype=np.float32), -1.0, 1.0)
+    """tensor2img(min_max=(-1, 1)) on [..., C] float32 rows: numpy's round is half to even.  A byte cannot carry a NaN and numpy's
+    cast of one to uint8 is undefined: a NaN element is byte 0, as srhip_diff_quant_u8 documents."""
+    v = np.asarray(x, dtype=np.float32)
+    v = np.clip(np.where(np.isnan(v), np.float32(-1.0), v), -1.0, 1.0)
     v = (v - np.float32(-1.0)) / np.float32(2.0)
     return (v * np.float32(255.0)).round().astype(np.uint8)
 

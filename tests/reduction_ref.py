@@ -262,6 +262,26 @@ def adam_ref(p, grads, lr, b1, b2, eps, grad_scale, clip):
     return out
 
 
+# hyper-parameters that fp32 holds exactly: the entry point takes them as floats, and 1 - b2 formed from a rounded 0.999 would be a
+# difference of the INPUTS (1.3e-5 of v), not of the kernel's arithmetic
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 2.0 ** -12, 0.875, 1 - 2.0 ** -8, 2.0 ** -27
+
+
+def adam_stock(p0, grads, clip, dtype, lr=ADAM_LR, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS):
+    """torch.optim.Adam on the CPU in `dtype`, then p.data.clamp_(-clip, clip) when clip > 0 (sradsgan.py:891-892).  Returns
+    [(p, exp_avg, exp_avg_sq) after each step]."""
+    q = p0.to(dtype).clone().requires_grad_()
+    opt = torch.optim.Adam([q], lr=lr, betas=(b1, b2), eps=eps)
+    steps = []
+    for g in grads:
+        q.grad = g.to(dtype).clone()
+        opt.step()
+        if clip > 0:
+            q.data.clamp_(-clip, clip)
+        steps.append((q.detach().clone(), opt.state[q]['exp_avg'].clone(), opt.state[q]['exp_avg_sq'].clone()))
+    return steps
+
+
 ADAM_GRAD_SCALES = (1.0, 1e-3, 1e-6, 0.0, 1.0)     # per step
 ADAM_FROZEN = 1000                                  # the first elements never receive a gradient: m = v = 0, denominator = eps
 

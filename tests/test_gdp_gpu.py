@@ -27,6 +27,11 @@ def rel_err(got, want):
     return float((got - want).abs().max() / want.abs().max().clamp_min(1e-30))
 
 
+def attention_bar(e32):
+    """The bar of the attention output: 4 x the error of the fp32 restatement, never below 1e-5."""
+    return max(1e-5, 4 * e32)
+
+
 def bits(t):
     return t.detach().cpu().contiguous().view(torch.int32)
 
@@ -103,7 +108,7 @@ def test_attention_matches_fp64(n, heads, ch, t):
     top = float(torch.einsum('bct,bcs->bts', q, k).max() / math.sqrt(ch))
     got = gdp.qkv_attention(qkv.to(DEV), heads)
     e = rel_err(got, want)
-    bar = max(1e-5, 4 * e32)
+    bar = attention_bar(e32)
     print('gdp attention %s: rel err %.2e, fp32 restatement %.2e, bar %.2e, largest logit %.1f' % ((n, heads, ch, t), e, e32, bar, top))
     if t >= 36:
         assert top > 30                                                       # the running-maximum rescale is exercised

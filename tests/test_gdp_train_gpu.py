@@ -25,6 +25,11 @@ GRAD_FACTOR = {'fp32': 10.0, 'bf16x3': 100.0}      # x the float32 CPU restateme
 LOSS_BAR = 1e-5
 
 
+def lse_bar(e32):
+    """The bar of the saved log-sum-exp: 4 x the error of the fp32 restatement, never below 2e-6."""
+    return max(2e-6, 4 * e32)
+
+
 def leaf(t):
     return t.detach().to(DEV).requires_grad_(True)
 
@@ -203,7 +208,7 @@ def test_attention_backward_matches_fp64(n, heads, ch, t, amp):
     bar = max(1e-5, 4 * e32)
     _, out_lse, lse = gdp_train.attention_fwd_lse(qkv.to(DEV), heads)
     el, el32 = rel_err(lse, lse64), rel_err(lse32, lse64)
-    lbar = max(2e-6, 4 * el32)
+    lbar = lse_bar(el32)
     print('gdp attention backward %s amp %g: dqkv rel err %.2e, fp32 restatement %.2e, bar %.2e; lse %.2e, fp32 %.2e, bar %.2e (largest %.1f)'
           % ((n, heads, ch, t), amp, e, e32, bar, el, el32, lbar, float(lse64.max())))
     assert tuple(qd.grad.shape) == tuple(qkv.shape) and e <= bar

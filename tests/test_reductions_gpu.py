@@ -386,9 +386,7 @@ def test_loss_wrappers_copy_views_the_kernels_would_refuse():
 # --------------------------------------------------------------------------------------------- #
 
 ADAM_N = 4 * (2048 * 256 + 3)        # float4 items: one grid-stride trip more than the 2048-block cap covers, for three items
-# hyper-parameters that fp32 holds exactly: the entry point takes them as floats, and 1 - b2 formed from a rounded 0.999 would be a
-# difference of the INPUTS (1.3e-5 of v), not of the kernel's arithmetic
-ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 2.0 ** -12, 0.875, 1 - 2.0 ** -8, 2.0 ** -27
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = R.ADAM_LR, R.ADAM_B1, R.ADAM_B2, R.ADAM_EPS      # exact in fp32 (tests/reduction_ref.py)
 
 
 @pytest.mark.parametrize('clip', [0.0, 0.05])
