@@ -1026,6 +1026,29 @@ int srhip_dihedral_f32(const float* x, const long* x_strides, float* y, const lo
 int srhip_ensemble_merge_f32(const float* const* views, const long* view_strides, const int* ops, int m, float* out,
                              const long* out_strides, int n, int c, int h, int w, void* stream);
 
+/* ABI 14 (additive) -- the blur-and-noise degradation of training batches (csrc/degrade.hip; sradsgan_amd/degrade.py; model/util.py:
+ * BatchBlur, b_GaussianNoising).  No atomics, re-runs are bit-identical, and no byte depends on the batch size or on a sample's place
+ * in the batch.  Argument errors return SRHIP_ERR_ARG before any launch.
+ *   srhip_blur_u8: in / out = uint8 [n][h][w][c] (c <= 4), kernels_dev = DEVICE float [n][l][l], l = 1..21 (even l allowed): sample k
+ *     cross-correlated with kernel k, every channel alike, on the image padded like nn.ReflectionPad2d (edge not repeated: i < 0 ->
+ *     -i, i >= H -> 2 (H - 1) - i) by lo = l / 2 before and hi = l / 2 (l odd) or l / 2 - 1 (l even) after; lo >= h or lo >= w is an
+ *     argument error.  The arithmetic is fixed: x = (float)byte / 255.0f; acc = 0.0f; for i = 0..l-1, inside it j = 0..l-1:
+ *     acc = acc + k[i][j] * xpad[y + i][x + j], product and sum each rounded to fp32 (no fma, one chain per output); the byte is
+ *     (unsigned char)(int)(acc * 255.0f) -- to_pil_image's mul(255).byte(), a truncation.  Whole dwords are stored, with scalar
+ *     heads and tails per row.
+ *   srhip_blur_f32: the same sum without the quantisation on a float tensor, logically x / y [n][c][h][w], each given by four
+ *     element strides {n, c, h, w} read on the HOST (NCHW-dense and channels-last alike).  per_sample = 0: one shared kernel [l][l]
+ *     (BatchBlur's 2-D branch), otherwise [n][l][l].  A NaN input reaches exactly the outputs whose l x l footprint holds it.
+ *   srhip_degrade_noise_u8: out = float [n][h][w][c] = min(max(x + z * level[k], 0), 1) with x = (float)byte / 255.0f, product and
+ *     sum rounded separately, level = DEVICE float [n]; z = a float tensor of out's shape or, with z == NULL and drawn != 0, the value
+ *     srhip_diff_randn(seed, step) writes for element ((k * h + y) * w + x) * c + ch.  level[k] == 0 gives srhip_u8_to_float's bits
+ *     for sample k.  A NaN (from a supplied z or a level) stays a NaN, as in torch.clamp.                                          */
+int srhip_blur_u8(const unsigned char* in, const float* kernels_dev, unsigned char* out, int n, int h, int w, int c, int l, void* stream);
+int srhip_blur_f32(const float* x, const long* x_strides, const float* kernels_dev, int per_sample, float* y, const long* y_strides, int n,
+                   int c, int h, int w, int l, void* stream);
+int srhip_degrade_noise_u8(const unsigned char* lr, const float* level_dev, const float* z, float* out, int n, int h, int w, int c,
+                           int drawn, unsigned long long seed, unsigned long long step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

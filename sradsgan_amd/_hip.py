@@ -244,6 +244,9 @@ SIGNATURES = {
     'srhip_augment_u8': (_i, [_vp] * 4 + [_i] * 5 + [ctypes.c_double, _i, _u64, _u64, _vp]),
     'srhip_dihedral_f32': (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
     'srhip_ensemble_merge_f32': (_i, [_vp, _vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp]),
+    'srhip_blur_u8': (_i, [_vp] * 3 + [_i] * 5 + [_vp]),
+    'srhip_blur_f32': (_i, [_vp, _vp, _vp, _i, _vp, _vp] + [_i] * 5 + [_vp]),
+    'srhip_degrade_noise_u8': (_i, [_vp] * 4 + [_i] * 5 + [_u64, _u64, _vp]),
 }
 
 _lib = None

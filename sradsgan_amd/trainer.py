@@ -27,6 +27,7 @@ import torch
 
 from . import checkpoint as ckpt
 from . import data as sdata
+from . import degrade as sdegrade
 from . import dp
 from . import lpips as slpips
 from . import ops
@@ -49,7 +50,12 @@ def default_args(**overrides):
              # not in main_sradsgan.py: the augmentation Dataset.__getitem__ offers (data.Augment; all off = no Augment is built)
              # and x8 geometric self-ensemble at validation (ensemble.SelfEnsemble)
              augment_random_crop=False, augment_rotate=False, augment_fliplr=False, augment_fliptb=False, augment_noise=None,
-             augment_seed=None, self_ensemble=False)
+             augment_seed=None, self_ensemble=False,
+             # not in main_sradsgan.py either: the blur-and-noise degradation of model/util.py (degrade.SRMDPreprocessing) in place
+             # of plain bicubic LR; degrade_blur off = nothing is built.  degrade_noise_high 0.0 = no noise kernel is launched
+             degrade_blur=False, degrade_kernel=21, degrade_random=True, degrade_sig=2.6, degrade_sig_min=0.2, degrade_sig_max=4.0,
+             degrade_rate_iso=1.0, degrade_scaling=3, degrade_noise_high=0.0, degrade_rate_cln=0.2, degrade_seed=None,
+             degrade_eval=False)
     d.update(overrides)
     return argparse.Namespace(**d)
 
@@ -98,6 +104,21 @@ def training_augment(args, rank=0):
     if not any(flags.values()):
         return None
     return sdata.Augment(args.crop_size, args.scale_factor, seed=getattr(args, 'augment_seed', None), rank=rank, **flags)
+
+
+def training_degrade(args, rank=0, test=False):
+    """The degrade.SRMDPreprocessing that `args.degrade_*` ask for -- per-sample Gaussian blur, bicubic down-sampling and noise of
+    model/util.py for uint8 training tiles -- or None when `degrade_blur` is off (an absent field is off): then nothing is built and
+    the trainer's batches are the plain bicubic ones.  test=True: the object for the test set, built only with `degrade_eval` on,
+    with the stable kernel of deviation `degrade_sig` and no noise, so that an evaluation is reproducible."""
+    if not getattr(args, 'degrade_blur', False) or (test and not getattr(args, 'degrade_eval', False)):
+        return None
+    g = lambda name, default: getattr(args, 'degrade_' + name, default)
+    noise_high = float(g('noise_high', 0.0))
+    return sdegrade.SRMDPreprocessing(args.scale_factor, random=bool(g('random', True)) and not test, kernel=g('kernel', 21),
+                                      noise=noise_high > 0.0 and not test, sig=g('sig', 2.6), sig_min=g('sig_min', 0.2),
+                                      sig_max=g('sig_max', 4.0), rate_iso=g('rate_iso', 1.0), scaling=g('scaling', 3),
+                                      rate_cln=g('rate_cln', 0.2), noise_high=noise_high, seed=g('seed', None), rank=rank)
 
 
 class SRADSGAN(object):
@@ -154,6 +175,8 @@ class SRADSGAN(object):
         self.rank, self.world = dp.rank_world()
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.augment = training_augment(args, self.rank)                            # None unless an augmentation switch is on
+        self.degrade = training_degrade(args, self.rank)                            # None unless args.degrade_blur is on
+        self.degrade_test = training_degrade(args, self.rank, test=True)            # None unless args.degrade_eval is on as well
         self.generator = self.discriminator = self.feature_extractor = None
         self.step = None
         self.log_dict = OrderedDict()
@@ -224,10 +247,15 @@ class SRADSGAN(object):
     def _batch(self, item, test=False):
         """(lr, hr, bc) device float tensors from a loader item: the reference's 4-tuple, a uint8 HR batch [B,H,W,3],
         or data.DevicePrefetcher's (uint8 batch, file names).  uint8 tiles get the reference's per-sample transforms
-        on the device: bicubic LR for training (dataset.py:418-436), bilinear LR for the test set (data.py:329-343)."""
+        on the device: bicubic LR for training (dataset.py:418-436), bilinear LR for the test set (data.py:329-343) -- or, with
+        args.degrade_blur on, the blurred and noisy LR of degrade.SRMDPreprocessing (the test set only with args.degrade_eval)."""
         if isinstance(item, (tuple, list)) and len(item) == 2 and torch.is_tensor(item[0]) and item[0].dtype == torch.uint8:
             item = item[0]
         if torch.is_tensor(item) and item.dtype == torch.uint8:
+            degrade = getattr(self, 'degrade_test' if test else 'degrade', None)
+            if degrade is not None:                                                 # blurred (and noisy) LR instead of plain bicubic
+                return sdegrade.degraded_training_batch(item.to(self.device), self.scale_factor, degrade,
+                                                        augment=None if test else getattr(self, 'augment', None))
             if not test and getattr(self, 'augment', None) is not None:              # training tiles only, never the test set
                 return sdata.augmented_training_batch(item.to(self.device), self.scale_factor, self.augment)
             make = sdata.test_batch if test else sdata.training_batch
