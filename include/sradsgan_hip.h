@@ -808,6 +808,37 @@ int srhip_ssim_u8(const float* a, const float* b, double* partial, int n, int h,
 int srhip_metric_finish(const unsigned long long* sse_partial, const double* ssim_partial, double* out, int n, int h, int w, int c,
                         double scale, void* stream);
 
+/* ---- evaluation by the papers' protocol (EDSR, RCAN, ESRGAN, SwinIR, HAT, BasicSR; calculate_psnr / calculate_ssim of
+ *      GDP_x0/core/metrics.py:109-160 with BasicSR's crop_border / test_y_channel switches).  Additive, ABI 14.
+ * a (test) and b (ground truth): [n][h][w][c] NHWC, c in {1, 3}; is_float = 0: uint8 bytes, 1: float32 in nominal [0, 1].
+ * Quantisation (is_float = 1 only): q = (uint8) rintf(fminf(fmaxf(x, 0), 1) * 255.f) -- the float32 product rounded half to even,
+ *   tensor2img with min_max = (0, 1), byte for byte what srhip_diff_quant_u8(lo 0, hi 1) writes.  A byte cannot carry a NaN: a NaN
+ *   element is quantised to byte 0; +inf -> 255, -inf -> 0.
+ * Crop: `crop` >= 0 rows and columns are removed on every side; the remaining h' x w' must be at least 11 x 11.
+ * Channels: luma = 0: the c channels as they are.  luma = 1 (needs c = 3): one channel, num = 65481 r + 128553 g + 24966 b as an exact
+ *   int32 and Y = 16.0 + num / 255000.0 in fp64, not rounded (BT.601 studio range, bgr2ycbcr(y_only=True); BasicSR passes Y through a
+ *   float32 intermediate, this library does not).
+ * MSE: mean over cropped pixels and channels of (a - b)^2 from an EXACT integer sum -- of squared byte differences, or in luma mode of
+ *   squared differences of num, divided by 255000^2; psnr = 10 log10(255^2 / mse), +inf where mse = 0.
+ * SSIM: g_i = exp(-(i - 5)^2 / 4.5) / sum, i = 0..10, in fp64; window g g^T.  At each of the (h' - 10)(w' - 10) positions whose window
+ *   lies inside the cropped image, per channel: mu_a, mu_b, E[a^2], E[b^2], E[ab] as window-weighted sums, s_a^2 = E[a^2] - mu_a^2,
+ *   s_b^2 likewise, s_ab = E[ab] - mu_a mu_b (population covariance), and
+ *   ((2 mu_a mu_b + C1)(2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1)(s_a^2 + s_b^2 + C2)), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2; the result
+ *   is the mean over positions and channels.  All fp64, products and sums separate (no contraction).
+ * Determinism: *partials partials per image, reduced in a fixed order, no atomics; an image's results have the same bits alone or in any
+ *   batch.
+ * pub_config: *partials = partials per image of the two passes, *tile = side of the SSIM kernel's tile of valid positions.
+ * pub_sse:  partial uint64 [n][*partials][2] = {sum of the low 32 bits, sum of the remaining high bits} of the squared differences.
+ * pub_ssim: partial double [n][*partials] = sums of the SSIM value over positions and channels.
+ * pub_finish: out = double [3][n], rows mse, psnr, ssim, from the two partial arrays in one launch. */
+int srhip_pub_config(int* partials, int* tile);
+int srhip_pub_sse(const void* a, const void* b, unsigned long long* partial, int n, int h, int w, int c, int crop, int luma, int is_float,
+                  void* stream);
+int srhip_pub_ssim(const void* a, const void* b, double* partial, int n, int h, int w, int c, int crop, int luma, int is_float,
+                   void* stream);
+int srhip_pub_finish(const unsigned long long* sse_partial, const double* ssim_partial, double* out, int n, int h, int w, int c, int crop,
+                     int luma, void* stream);
+
 /* ---- LPIPS, the fourth validation metric (sradsgan.py:561 `PerceptualLoss('net-lin', 'alex')`, called per image at :1125-1132 and
  *      :1326-1332; utils/PerceptualSimilarity/__init__.py:26-44, networks_basic.py:64-105, pretrained_networks.py:57-96).  Forward only.
  * lpips_stem: the scaling layer and AlexNet features[0:2] in one pass.  x [m][h][w][3] in [0,1] (normalize != 0: x = 2x - 1 first,

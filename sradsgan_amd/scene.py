@@ -238,3 +238,28 @@ def super_resolve_scene(generator, scene_u8, scale, tile, overlap, tiles_per_bat
     finally:
         generator.train(was_training)
     return blender.out
+
+
+def evaluate_scene(generator, hr_scene_u8, scale, tile, overlap, crop_border=None, y_channel=True, tiles_per_batch=16):
+    """The papers' evaluation of a whole ground-truth scene: hr_scene_u8, uint8 [H, W, 3] with H and W multiples of `scale` (host or
+    device), is reduced by `scale` with data.resize_u8 (Pillow-exact bicubic), super-resolved by super_resolve_scene(generator, LR,
+    scale, tile, overlap, tiles_per_batch) and compared with the scene by metrics.published_metrics_u8(crop_border, y_channel);
+    crop_border None = scale.  The same metrics are computed for the bicubic enlargement of the LR scene.
+    Returns {'sr': {mse, psnr, ssim}, 'bicubic': {mse, psnr, ssim}, 'out': the uint8 SR scene}, metric values float64 [1] on the device."""
+    from . import data as sdata, metrics as pub, ops
+    hr = _require_scene(hr_scene_u8, 'evaluate_scene')
+    scale = int(scale)
+    if scale <= 0 or hr.shape[0] % scale or hr.shape[1] % scale:
+        raise ValueError('evaluate_scene: the HR scene %dx%d is not a multiple of scale %d' % (hr.shape[0], hr.shape[1], scale))
+    crop_border = scale if crop_border is None else crop_border
+    param = next(iter(generator.parameters()), None)
+    if param is None:
+        raise ValueError('evaluate_scene: the generator has no parameters to tell its device from')
+    ops._require_gpu(param, 'evaluate_scene')
+    hr = hr.to(param.device).contiguous()
+    h, w = hr.shape[:2]
+    lr = sdata.resize_u8(hr[None], h // scale, w // scale, 'bicubic')
+    out = super_resolve_scene(generator, lr[0], scale, tile, overlap, tiles_per_batch)
+    bicubic = sdata.resize_u8(lr, h, w, 'bicubic')[0]
+    return {'sr': pub.published_metrics_u8(out, hr, crop_border, y_channel),
+            'bicubic': pub.published_metrics_u8(bicubic, hr, crop_border, y_channel), 'out': out}

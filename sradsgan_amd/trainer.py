@@ -55,7 +55,10 @@ def default_args(**overrides):
              # of plain bicubic LR; degrade_blur off = nothing is built.  degrade_noise_high 0.0 = no noise kernel is launched
              degrade_blur=False, degrade_kernel=21, degrade_random=True, degrade_sig=2.6, degrade_sig_min=0.2, degrade_sig_max=4.0,
              degrade_rate_iso=1.0, degrade_scaling=3, degrade_noise_high=0.0, degrade_rate_cln=0.2, degrade_seed=None,
-             degrade_eval=False)
+             degrade_eval=False,
+             # not in main_sradsgan.py: validation numbers by the papers' protocol (sradsgan_amd.metrics) beside the reference trainer's
+             # own; 'reference' = nothing new runs.  eval_crop_border None = scale_factor
+             eval_protocol='reference', eval_crop_border=None, eval_y_channel=True)
     d.update(overrides)
     return argparse.Namespace(**d)
 
@@ -92,6 +95,27 @@ def attention_ablation(args):
     if not isinstance(opts['addconv'], bool):
         raise ValueError('args.addconv must be a bool, got %r' % (opts['addconv'],))
     return opts
+
+
+EVAL_PROTOCOLS = ('reference', 'published')
+
+
+def evaluation_protocol(args):
+    """The validation protocol read from `args`, absent fields at their defaults: None for eval_protocol 'reference' -- the reference
+    trainer's own numbers and nothing else -- or, for 'published', the dict(crop_border, y_channel) that validate.evaluate takes to add
+    the papers' PSNR / SSIM (sradsgan_amd.metrics): `eval_crop_border` pixels shaved from every border (default scale_factor) and, with
+    `eval_y_channel` (default True), the BT.601 luma instead of RGB.  Anything else is a ValueError."""
+    name = getattr(args, 'eval_protocol', 'reference')
+    if name not in EVAL_PROTOCOLS:
+        raise ValueError('args.eval_protocol must be one of %r, got %r' % (EVAL_PROTOCOLS, name))
+    crop, y = getattr(args, 'eval_crop_border', None), getattr(args, 'eval_y_channel', True)
+    if crop is None:
+        crop = args.scale_factor
+    if isinstance(crop, bool) or not isinstance(crop, int) or crop < 0:
+        raise ValueError('args.eval_crop_border must be None or a non-negative integer, got %r' % (crop,))
+    if not isinstance(y, bool):
+        raise ValueError('args.eval_y_channel must be a bool, got %r' % (y,))
+    return None if name == 'reference' else dict(crop_border=crop, y_channel=y)
 
 
 def training_augment(args, rank=0):
@@ -140,6 +164,7 @@ class SRADSGAN(object):
                 raise ValueError('--%s must be one of %s, got %r' % (name, choices, value))
         self._check_loss_options()
         self.attention = attention_ablation(args)
+        self.eval_protocol = evaluation_protocol(args)          # None, or the papers' protocol beside the reference's (validation)
         # the discriminator's normalisation (base_networks.Discriminator's norm_type, the line the reference keeps as a comment at
         # sradsgan.py:672): absent / None = this trainer's own BatchNorm discriminator, else model.discriminators.PatchDiscriminator
         self.d_norm_type = getattr(args, 'd_norm_type', None)
@@ -366,6 +391,11 @@ class SRADSGAN(object):
         metrics = ('mse', 'psnr', 'ssim', 'ergas') + (() if lpips is None else ('lpips',))
         if lpips is not None:
             sums['bicubic_lpips'] = sums[label + '_lpips'] = 0.0
+        protocol = getattr(self, 'eval_protocol', None)
+        if protocol is not None:
+            metrics += ('pub_psnr', 'pub_ssim')
+            for prefix in ('bicubic', label):
+                sums[prefix + '_pub_psnr'] = sums[prefix + '_pub_ssim'] = 0.0
         img_num = 0
         was_training, inner = generator.training, generator
         if getattr(self, 'self_ensemble', False):                                                # the "+" protocol: 8 views, merged
@@ -374,7 +404,7 @@ class SRADSGAN(object):
         start = time.time()
         for item in loader:
             imgs_lr, imgs_hr, imgs_bc = self._batch(item, test=True)
-            out = sval.evaluate(generator, imgs_lr, imgs_hr, self.scale_factor, bicubic=imgs_bc, lpips=lpips)
+            out = sval.evaluate(generator, imgs_lr, imgs_hr, self.scale_factor, bicubic=imgs_bc, lpips=lpips, protocol=protocol)
             img_num += imgs_hr.size(0)
             for k in metrics:
                 sums['bicubic_' + k] += float(out['bicubic'][k].sum())
@@ -393,6 +423,9 @@ class SRADSGAN(object):
             for k in ('mse', 'psnr', 'ssim', 'ergas'):
                 rlt['%s_%s' % (prefix, k)] = avg['%s_%s' % (prefix, k)]
             rlt['%s_lpips' % prefix] = avg.get('%s_lpips' % prefix, float('nan'))
+            if getattr(self, 'eval_protocol', None) is not None:                                 # the papers' numbers, after the LPIPS slot
+                for k in ('pub_psnr', 'pub_ssim'):
+                    rlt['%s_%s' % (prefix, k)] = avg['%s_%s' % (prefix, k)]
         if self.rank != 0:
             return
         os.makedirs(self.save_dir, exist_ok=True)

@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _hip, ops
+from . import metrics as pub
 
 
 def _p(t):
@@ -38,11 +39,14 @@ def quantized_metrics(sr, hr, scale):
 
 
 @torch.no_grad()
-def evaluate(generator, lr, hr, scale, bicubic=None, lpips=None):
+def evaluate(generator, lr, hr, scale, bicubic=None, lpips=None, protocol=None):
     """One validation batch: recon = G(lr) (sradsgan.py:1305), metrics of recon vs hr and -- when the
     bicubic-upsampled input is given -- of bicubic vs hr (:1328-1331).  Returns per-image metric dicts.
     lpips: an lpips.LPIPS model; then out['sr']['lpips'] (and out['bicubic']['lpips']) are float64 [N] of the unquantised
-    images (:1326-1332), the backbone running once over [recon; hr; bicubic]."""
+    images (:1326-1332), the backbone running once over [recon; hr; bicubic].
+    protocol: None, or dict(crop_border=k, y_channel=bool): then out['sr'] (and out['bicubic']) also carry pub_mse, pub_psnr and
+    pub_ssim, metrics.published_metrics of the same images -- the papers' protocol beside the reference trainer's, whose keys are
+    computed exactly as without it."""
     recon = generator(lr)
     out = {'recon': recon, 'sr': quantized_metrics(recon, hr, scale)}
     if bicubic is not None:
@@ -54,6 +58,10 @@ def evaluate(generator, lr, hr, scale, bicubic=None, lpips=None):
         out['sr']['lpips'] = d[:n]
         if bicubic is not None:
             out['bicubic']['lpips'] = d[n:]
+    if protocol is not None:
+        for key, img in (('sr', recon),) + (() if bicubic is None else (('bicubic', bicubic),)):
+            m = pub.published_metrics(img, hr, protocol['crop_border'], protocol['y_channel'])
+            out[key].update(pub_mse=m['mse'], pub_psnr=m['psnr'], pub_ssim=m['ssim'])
     return out
 
 
@@ -65,8 +73,9 @@ class GraphedEvaluator:
     Weights are read at replay time, so an evaluator stays valid across training steps as long as the parameter
     storage does not move (ParamArena guarantees that) and ops.repack_all() has run after the last update."""
 
-    def __init__(self, generator, scale, warmup=2, lpips=None):
+    def __init__(self, generator, scale, warmup=2, lpips=None, protocol=None):
         self.generator, self.scale, self.warmup, self.lpips = generator, scale, warmup, lpips
+        self.protocol = None if protocol is None else dict(crop_border=protocol['crop_border'], y_channel=bool(protocol['y_channel']))
         self._graphs = {}
 
     def _capture(self, key, lr, hr, bicubic):
@@ -75,16 +84,18 @@ class GraphedEvaluator:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # library / allocator / packed-weight warm-up outside the capture
             for _ in range(self.warmup):
-                evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips)
+                evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips, self.protocol)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips)
+            out = evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips, self.protocol)
         self._graphs[key] = (graph, static, out)
 
     def __call__(self, lr, hr, bicubic=None):
         ops._require_gpu(lr, 'GraphedEvaluator')
         key = (tuple(lr.shape), tuple(hr.shape), bicubic is not None, ops.get_conv_math())
+        if self.protocol is not None:                 # `protocol` may be reassigned between calls: one capture per value
+            key += (self.protocol['crop_border'], bool(self.protocol['y_channel']))
         if key not in self._graphs:
             self._capture(key, lr, hr, bicubic)
         graph, static, out = self._graphs[key]
