@@ -30,12 +30,16 @@ def save_epoch_network(save_dir, network, network_label, iter_label):
     return path
 
 
-def _after_load():
+def _after_load(*networks):
     # parameters are views into flat arenas and convs cache re-packed weights: loading writes in place, then the packs
-    # must be refreshed (sradsgan_amd.ops is only needed when the HIP library is present)
+    # must be refreshed (sradsgan_amd.ops is only needed when the HIP library is present).  With the loaded networks named, every cached
+    # copy of their weights is refreshed (static nets included); without, the batched re-pack of all registered trainable weights runs.
     try:
         from . import ops
-        ops.bump_weight_epoch()
+        if networks:
+            ops.weights_changed(*networks)
+        else:
+            ops.bump_weight_epoch()
     except Exception:                                   # CPU-only use (tests of the host logic)
         pass
 
@@ -44,7 +48,7 @@ def load_epoch_network(load_path, network, strict=True):
     """sradsgan.py:1054-1058.  Copies into the existing parameter storage (arena views stay valid)."""
     state = torch.load(load_path, map_location='cpu')
     result = _unwrap(network).load_state_dict(state, strict=strict)
-    _after_load()
+    _after_load(_unwrap(network))
     return result
 
 
@@ -64,7 +68,7 @@ def load_model(save_dir, generator):
     if not os.path.exists(path):
         return False
     _unwrap(generator).load_state_dict(torch.load(path, map_location='cpu'), strict=False)
-    _after_load()
+    _after_load(_unwrap(generator))
     return True
 
 
@@ -86,7 +90,7 @@ def load_compatible(network, state_dict):
                 dst.copy_(state_dict[k])
                 loaded.append(k)
     unused = [k for k in state_dict if k not in own]
-    _after_load()
+    _after_load(net)
     return loaded, missing, mismatch, unused
 
 

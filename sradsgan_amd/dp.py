@@ -41,6 +41,7 @@ class ParamArena:
             offs.append(total)
             total += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
         self.params, self.offsets, self.numel = params, offs, total
+        self._static_seen, self._static_params = None, ()
         self.flat_p = torch.zeros(total, device=dev, dtype=torch.float32)
         self.flat_g = torch.zeros(total, device=dev, dtype=torch.float32)
         self.exp_avg = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -65,6 +66,13 @@ class ParamArena:
         _hip.check(_hip.lib().srhip_adam_step(_p(self.flat_p), _p(self.flat_g), _p(self.exp_avg), _p(self.exp_avg_sq), _p(self.step_state),
                                               self.numel, float(lr), float(b1), float(b2), float(eps), float(grad_scale), float(clip),
                                               _stream()), 'adam_step')
+        # parameters marked static (ops.mark_static) are outside the batched re-pack: their images are packed again at their next use
+        from . import ops
+        if self._static_seen != ops._static_gen:
+            self._static_seen = ops._static_gen
+            self._static_params = [p for p in self.params if getattr(p, '_srhip_static', False)]
+        if self._static_params:
+            ops.invalidate_static(self._static_params)
 
     def check_views(self):
         """True while every parameter and gradient still aliases the arena (module.to()/zero_grad(

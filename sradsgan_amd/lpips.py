@@ -63,7 +63,6 @@ class LPIPS(nn.Module):
             for k, c in enumerate(CHANNELS):
                 self.lin(k).fill_(1.0 / c)
         ops.mark_static(self)
-        self._stem = None                                          # (weight version, data_ptr, HWIO copy)
         self._pair_lists = {}
         self.eval()
 
@@ -102,10 +101,8 @@ class LPIPS(nn.Module):
         return self._load(named, 'load_lin')
 
     def _stem_weight(self):
-        w = self.features[0].weight
-        if self._stem is None or self._stem[0] != w._version or self._stem[1] != w.data_ptr():
-            self._stem = (w._version, w.data_ptr(), w.detach().permute(2, 3, 1, 0).contiguous())     # [ky][kx][ci][co]
-        return self._stem[2]
+        # [ky][kx][ci][co], kept on the parameter beside its packed images: ops.weights_changed refreshes it with them
+        return ops.derived_weight(self.features[0].weight, 'hwio', lambda w: w.detach().permute(2, 3, 1, 0).contiguous())
 
     def _pairs_tensor(self, index_pairs, m, device):
         key = (tuple(map(tuple, index_pairs)), str(device))

@@ -32,6 +32,12 @@ def _unit(x):
     return x / (x.norm() + 1e-12)
 
 
+def _same_layers(table, layers):
+    """False once the module holds other Parameter objects than the table was built from (load_state_dict(assign=True) replaces them):
+    the table would go on reading the ones that have left."""
+    return len(table.layers) == len(layers) and all(a is b for old, new in zip(table.layers, layers) for a, b in zip(old, new))
+
+
 class SpectralNorm(nn.Module):
     def __init__(self, module, name='weight', power_iterations=1):
         super().__init__()
@@ -60,7 +66,7 @@ class SpectralNorm(nn.Module):
     def forward(self, x, act_slope=None, residual=None, weight=None):
         """weight: this pass's effective weight when the owner has already run the batched call for all its wrappers."""
         if weight is None:
-            if self._table is None:
+            if self._table is None or not _same_layers(self._table, [self.layer()]):
                 self._table = ops.SpectralTable([self.layer()])
             weight, = ops.spectral_weights(self._table)
         m = self.module
@@ -74,9 +80,10 @@ def spectral_init_(net, std=0.02):
     wrapped = {id(m.module) for m in net.modules() if isinstance(m, SpectralNorm)}
     for m in net.modules():
         if isinstance(m, SpectralNorm):
-            m.module.weight_bar.data.normal_(0.0, std)
-            if m.module.bias is not None:
-                m.module.bias.data.zero_()
+            with torch.no_grad():                # on the parameters, not `.data`: the write must move their version
+                m.module.weight_bar.normal_(0.0, std)
+                if m.module.bias is not None:
+                    m.module.bias.zero_()
         elif id(m) not in wrapped:
             weights_init_normal(m)
     return net
@@ -115,8 +122,9 @@ class SpectralPatchDiscriminator(nn.Module):
         return [self.model[conv_i] for conv_i, _, _ in self._blocks]
 
     def forward(self, img):
-        if self._table is None:
-            self._table = ops.SpectralTable([sn.layer() for sn in self.spectral_layers()])
+        layers = [sn.layer() for sn in self.spectral_layers()]
+        if self._table is None or not _same_layers(self._table, layers):
+            self._table = ops.SpectralTable(layers)
         weights = ops.spectral_weights(self._table)          # one power iteration of all 8 layers: u and v advance here
         x = ops.nhwc(img)
         m = self.model

@@ -16,11 +16,11 @@ from .sradsgan import FeatureExtractor  # noqa: F401  (re-exported: srgan.py:44-
 def weights_init_normal(m):
     """srgan.py:36-42: conv weights N(0, .02) (biases untouched), BatchNorm weights N(1, .02), biases 0."""
     name = m.__class__.__name__
-    if name.find('Conv') != -1:
-        torch.nn.init.normal_(m.weight.data, 0.0, 0.02)
+    if name.find('Conv') != -1:                  # on the parameters, not `.data`: the write must move their version (ops.packed_weight)
+        torch.nn.init.normal_(m.weight, 0.0, 0.02)
     elif name.find('BatchNorm') != -1:
-        torch.nn.init.normal_(m.weight.data, 1.0, 0.02)
-        torch.nn.init.constant_(m.bias.data, 0.0)
+        torch.nn.init.normal_(m.weight, 1.0, 0.02)
+        torch.nn.init.constant_(m.bias, 0.0)
 
 
 class _ShuffleRelu(nn.Module):

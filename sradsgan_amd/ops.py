@@ -265,6 +265,21 @@ class _PackRegistry:
 _registry = _PackRegistry()
 
 
+class _Slots(dict):
+    """mode -> registry entry, the `_srhip_packed` attribute of a Parameter.  An entry holds a weak reference, an event and a device
+    buffer that belong to THIS Parameter object: a pickle (torch.save(module)) or a copy of the Parameter takes its __dict__ along,
+    so the dict pickles and copies as an empty one -- the copy packs its own images on first use and registers them itself."""
+
+    def __reduce__(self):
+        return (_Slots, ())
+
+    def __deepcopy__(self, memo):
+        return _Slots()
+
+    def __copy__(self):
+        return _Slots()
+
+
 def _wshape(w):
     """OIHW shape of a conv weight; a Linear weight [out, in] is the 1x1 conv [out, in, 1, 1] (same memory)."""
     return tuple(w.shape) if w.dim() == 4 else (w.shape[0], w.shape[1], 1, 1)
@@ -285,6 +300,10 @@ def repack_all():
         return
     lib = _hip.lib()
     live = [ent[0]() for ent in reg.entries]
+    if not reg.dirty:
+        # a parameter re-homed since the table was built (dp.ParamArena adopting a net that has run, `p.data = ...`) and not used since:
+        # the table would read the storage it has left
+        reg.dirty = any(ent[3] != w.data_ptr() for ent, w in zip(reg.entries, live))
     if reg.dirty or reg.table is None:
         import struct
         assert lib.srhip_pack_entry_bytes() == 40
@@ -335,15 +354,22 @@ def _pack_event(ent):
     ent[5], ent[6], ent[7] = ev, torch.cuda.current_stream().cuda_stream, set()
 
 
+_static_gen = 0                  # moves with every mark_static / mark_trainable: dp.ParamArena looks for static parameters again
+
+
 def mark_static(module):
     """Parameters of `module` are never updated (VGG): pack once, keep out of the per-step batched repack."""
+    global _static_gen
     for p in module.parameters():
         p._srhip_static = True
+    _static_gen += 1
 
 
 def mark_trainable(module):
     """The inverse of mark_static: the static mark goes, and packed images made so far (a frozen net that has run, or one that has
     trained before) are dropped and leave the batched re-pack, so that the next use packs the weights again and registers them."""
+    global _static_gen
+    _static_gen += 1
     dropped = set()
     for p in module.parameters():
         dropped.update(id(ent) for ent in getattr(p, '_srhip_packed', {}).values())
@@ -369,7 +395,7 @@ def packed_weight(w, mode):
         return packed
     slots = getattr(w, '_srhip_packed', None)
     if slots is None:
-        slots = w._srhip_packed = {}
+        slots = w._srhip_packed = _Slots()
     ent = slots.get(mode)
     if ent is None or ent[3] != w.data_ptr():
         packed = torch.empty(lib.srhip_packed_elems(cout, cin, kh, kw, mode), device=w.device, dtype=torch.float32)
@@ -395,6 +421,74 @@ def packed_weight(w, mode):
     else:
         _pack_fence(ent)
     return ent[2]
+
+
+def _parameters_of(things):
+    seen, out = set(), []
+    for t in things:
+        for p in (t.parameters() if isinstance(t, torch.nn.Module) else (t,)):
+            if not isinstance(p, torch.Tensor):
+                raise TypeError('weights_changed: modules or parameters, got %s' % type(p).__name__)
+            if id(p) not in seen:
+                seen.add(id(p))
+                out.append(p)
+    return out
+
+
+def invalidate_static(params):
+    """Host only: the images of the static parameters among `params` are packed again at their next use.  For a writer that goes through
+    raw pointers (dp.ParamArena.adam_step): static images are outside the batched re-pack that bump_weight_epoch runs."""
+    for p in params:
+        for ent in getattr(p, '_srhip_packed', {}).values():
+            ent[4] = -1
+
+
+def weights_changed(*modules_or_parameters):
+    """Call after writing parameters in a way torch does not report: `p.data.normal_()`, `p.data.clamp_()`, `torch.nn.init.*_(p.data)`,
+    `torch._foreach_*_([p.data])`, an EMA through `.data`, a raw-pointer kernel -- none of them moves `p._version` (INTEGRATION.md,
+    "changing weights outside the trainer").  Brings every cached copy of the named parameters (all parameters of a module) up to date on
+    the current stream: the packed images of both kinds, those of static nets included, and copies derived from a weight (the LPIPS stem).
+    The images are rewritten in place, so a captured graph that reads them sees the new weights at its next replay.  Ordering: a stream
+    that has already used an image waits for the new pack's event at its next use (_pack_fence); reads of the old image still in flight
+    on another stream are the caller's to order, as for any write to the weights themselves."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    for p in _parameters_of(modules_or_parameters):
+        for got in getattr(p, '_srhip_derived', {}).values():
+            _refresh_derived(p, got)
+        eff = getattr(p, '_srhip_eff_packed', None)
+        if eff:                                   # an effective weight of ops.spectral_weights that was edited: packed again at its next use
+            eff.clear()
+        slots = getattr(p, '_srhip_packed', None)
+        if not slots:
+            continue
+        for mode, ent in list(slots.items()):
+            if ent[3] != p.data_ptr():            # re-homed as well: packed_weight makes a new image and keeps the registry right
+                packed_weight(p, mode)
+                continue
+            _pack_fence(ent)
+            _pack_now(p, mode, ent[2])
+            ent[4] = p._version
+            if not capturing:
+                _pack_event(ent)
+
+
+def derived_weight(w, key, make):
+    """A copy derived from parameter `w` (`make(w)`, e.g. the HWIO stem weight of lpips.LPIPS), kept on the parameter object and rebuilt
+    when w's version or storage moves, or when weights_changed names w."""
+    cache = getattr(w, '_srhip_derived', None)
+    if cache is None:
+        cache = w._srhip_derived = _Slots()
+    got = cache.get(key)
+    if got is None:
+        got = cache[key] = [w._version, w.data_ptr(), make(w), make]
+    elif got[0] != w._version or got[1] != w.data_ptr():
+        _refresh_derived(w, got)
+    return got[2]
+
+
+def _refresh_derived(w, got):
+    got[2].copy_(got[3](w))                       # in place: a captured graph reads this buffer
+    got[0], got[1] = w._version, w.data_ptr()
 
 
 eff_pack_stats = {'packed': 0, 'reused': 0}       # effective-weight images packed / found again (tests, tools/time_spectral.py)
@@ -1675,6 +1769,8 @@ def _tail_forward_eval(u, skip, fc1_w, fc2_w, w7, wc, bc, pool=None):
     n, c, h, w = u.shape
     lib = _hip.lib()
     out = torch.empty_like(u, memory_format=CL)
+    if bc is not None:
+        bc = _dense16(bc.detach())                # a parameter may be a view at any offset (torch.nn.utils.vector_to_parameters): the kernel reads float4
     if pool is not None:
         _hip.check(lib.srhip_attn_tail_eval_pooled(_p(u), _p(skip), _p(pool[0]), pool[1], pool[2], _p(fc1_w.detach().contiguous()),
                                                    _p(fc2_w.detach().contiguous()), _p(w7.detach().contiguous()), _p(packed_weight(wc, 0)),

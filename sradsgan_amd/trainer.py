@@ -65,15 +65,18 @@ def default_args(**overrides):
 
 def weights_init_normal(m, mean=0.0, std=0.02):
     """utils/utils.py:97-114 (applied at sradsgan.py:713-714)."""
+    # written through the parameters themselves, not `.data`: the write moves their version, which is what the packed weight images of a
+    # net that has already run are refreshed by (ops.packed_weight)
     name = m.__class__.__name__
-    if name.find('Linear') != -1 or name.find('Conv2d') != -1 or name.find('ConvTranspose2d') != -1:
-        m.weight.data.normal_(mean, std)
-        if m.bias is not None:
-            m.bias.data.zero_()
-    elif name.find('BatchNorm') != -1:
-        m.weight.data.normal_(1.0, 0.02)
-        if m.bias is not None:
-            m.bias.data.zero_()
+    with torch.no_grad():
+        if name.find('Linear') != -1 or name.find('Conv2d') != -1 or name.find('ConvTranspose2d') != -1:
+            m.weight.normal_(mean, std)
+            if m.bias is not None:
+                m.bias.zero_()
+        elif name.find('BatchNorm') != -1:
+            m.weight.normal_(1.0, 0.02)
+            if m.bias is not None:
+                m.bias.zero_()
 
 
 ATTENTION_MODES = ('',) + tuple(ops.TAIL_ORDERS)       # la_mode / ga_mode of sradsgan.py:215-324, 365-439: '', CA-SA, SA-CA, CA, SA, CA|SA

@@ -70,8 +70,15 @@ class GraphedEvaluator:
     (about 500 kernels of ~10 us for a batch of 16: the GPU waits for the Python launch loop), so the whole
     forward + metric pass is captured once per input shape and replayed; inputs are copied into the capture's static
     buffers, results live in static buffers that the next call overwrites (clone what must survive).
-    Weights are read at replay time, so an evaluator stays valid across training steps as long as the parameter
-    storage does not move (ParamArena guarantees that) and ops.repack_all() has run after the last update."""
+    Weights are read at replay time -- the parameters themselves and the packed images ops.packed_weight keeps of them --, and a replay
+    runs none of the Python that keeps those images fresh.  So every call first compares, on the host, what the capture recorded with
+    what the parameters (generator and LPIPS model) say now:
+      * a `_version` that moved since the image was packed (load_state_dict, a torch optimiser, an initialiser): the images of that
+        parameter are packed again in place (ops.weights_changed), then the graph is replayed;
+      * a `data_ptr()` that moved (dp.ParamArena built after the capture, `p.data = ...`): the capture reads storage the parameter has
+        left, so the captures are dropped and the call captures again -- it never returns numbers of the old weights.
+    Writes torch cannot see (the fused Adam, `.data` writes) need what they need everywhere: ops.bump_weight_epoch() /
+    ops.weights_changed() after them.  In the steady state the comparison launches nothing."""
 
     def __init__(self, generator, scale, warmup=2, lpips=None, protocol=None):
         self.generator, self.scale, self.warmup, self.lpips = generator, scale, warmup, lpips
@@ -90,12 +97,34 @@ class GraphedEvaluator:
         with torch.cuda.graph(graph):
             out = evaluate(self.generator, static['lr'], static['hr'], self.scale, static['bicubic'], self.lpips, self.protocol)
         self._graphs[key] = (graph, static, out)
+        self._params = self._parameters()
+        self._ptrs = [p.data_ptr() for p in self._params]
+
+    def _parameters(self):
+        nets = [self.generator] + ([] if self.lpips is None else [self.lpips])
+        return [p for net in nets for p in net.parameters()]
+
+    def _follow_weights(self):
+        """Host only unless something has changed (class docstring).  False: the captures were dropped."""
+        params = self._parameters()
+        if len(params) != len(self._params) or any(a is not b for a, b in zip(params, self._params)) \
+                or any(p.data_ptr() != ptr for p, ptr in zip(params, self._ptrs)):
+            self._graphs.clear()
+            return False
+        stale = [p for p in params
+                 if any(ent[4] != p._version for ent in getattr(p, '_srhip_packed', {}).values())
+                 or any(got[0] != p._version for got in getattr(p, '_srhip_derived', {}).values())]
+        if stale:
+            ops.weights_changed(*stale)
+        return True
 
     def __call__(self, lr, hr, bicubic=None):
         ops._require_gpu(lr, 'GraphedEvaluator')
         key = (tuple(lr.shape), tuple(hr.shape), bicubic is not None, ops.get_conv_math())
         if self.protocol is not None:                 # `protocol` may be reassigned between calls: one capture per value
             key += (self.protocol['crop_border'], bool(self.protocol['y_channel']))
+        if self._graphs:
+            self._follow_weights()
         if key not in self._graphs:
             self._capture(key, lr, hr, bicubic)
         graph, static, out = self._graphs[key]
