@@ -65,7 +65,8 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *         RCAN; HAT's window-transformer passes (srhip_hat_*: LayerNorm, GELU, window attention, channel attention at any
  *         C <= 128 and the block combine).  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
  *         declared symbol by name when it loads the library, so a library without them fails at load time.
- *         The LPIPS metric's passes (srhip_lpips_*, srhip_maxpool3x3s2_fwd) joined the same way: additive, version 14. */
+ *         The LPIPS metric's passes (srhip_lpips_*, srhip_maxpool3x3s2_fwd) joined the same way: additive, version 14; so did the
+ *         backward passes that make it a loss (srhip_lpips_head_bwd, srhip_maxpool3x3s2_bwd, srhip_lpips_stem_bwd). */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -840,7 +841,7 @@ int srhip_pub_finish(const unsigned long long* sse_partial, const double* ssim_p
                      int luma, void* stream);
 
 /* ---- LPIPS, the fourth validation metric (sradsgan.py:561 `PerceptualLoss('net-lin', 'alex')`, called per image at :1125-1132 and
- *      :1326-1332; utils/PerceptualSimilarity/__init__.py:26-44, networks_basic.py:64-105, pretrained_networks.py:57-96).  Forward only.
+ *      :1326-1332; utils/PerceptualSimilarity/__init__.py:26-44, networks_basic.py:64-105, pretrained_networks.py:57-96).  The forward passes:
  * lpips_stem: the scaling layer and AlexNet features[0:2] in one pass.  x [m][h][w][3] in [0,1] (normalize != 0: x = 2x - 1 first,
  *   __init__.py:36-38) -> (x - shift) / scale per channel (networks_basic.py:101-105) on in-image taps only -- the conv pads with zeros
  *   in the scaled space -- then conv 3->64 k11 s4 p2 + bias + ReLU in exact fp32 in every conv-math mode.
@@ -858,6 +859,27 @@ int srhip_lpips_blocks(void);
 int srhip_lpips_head(const float* f, const int* pairs, const float* w, double* partial, int m, int npairs, int h, int wd, int c,
                      void* stream);
 int srhip_lpips_finish(const double* partial, const long* tap_pixels, int ntaps, int npairs, double* out, void* stream);
+/* Additive, ABI stays 14 -- LPIPS as a loss (lpips.LPIPS.loss): the three backward passes that the conv kernels do not cover.  Exact
+ * fp32 in every conv-math mode, no atomics, one fixed summation order per value, nothing that crosses images.  (The version number
+ * does not move, as for the forward passes: the binding resolves every declared symbol when it loads the library.)
+ * lpips_head_bwd: one tap's gradient with respect to the PRED features -- pairs[p] = (target index, pred index) into m -- already
+ *   passed back through that tap's ReLU; df [npairs][h][w][c].  Per pixel, f = pred, t = target, n = sqrt(sum f^2), D = n + 1e-10,
+ *   e_c = f_c / D - t_c / D_t, q_c = 2 w_c e_c s, S = sum_c q_c f_c, df_c = q_c / D - f_c S / (D^2 n); s = upstream[0] * inv_count
+ *   with upstream a device scalar (no host sync) and inv_count = 1 / (N h w).  f_c <= 0 writes 0, so a NaN feature passes its NaN on
+ *   like ATen's threshold_backward.  A pixel with n == 0 writes zeros and never forms 0 / 0: every channel is masked there anyway;
+ *   torch autograd yields NaN at such a pixel, and the departure is deliberate.  C % 4 == 0.
+ * maxpool3x3s2_bwd: backward of nn.MaxPool2d(3, 2) in gather form, fused with what follows it: dx = gather(dy) * [x > 0] + residual.
+ *   x [n][h][w][c] is the pool's input; each input pixel recomputes the arg-max of the at most 2 x 2 windows that hold it in the
+ *   forward's scan order (the first maximum wins) and adds their dy in ascending (oy, ox) order.  relu != 0 applies the mask of x (a
+ *   ReLU output; x <= 0 writes 0); residual may be NULL.
+ * lpips_stem_bwd: the stem's data gradient to the image, scaling layer included: g [m][ho][wo][64] is the gradient at the stem conv's
+ *   output (ReLU mask applied), dx [m][h][w][3] = (normalize ? 2 : 1) / scale[ch] * conv_transpose(g, w).  Gather form: at most 3 x 3
+ *   output positions x 64 channels, one fmaf chain per value with (oy, ox, co) ascending.                                          */
+int srhip_lpips_head_bwd(const float* f, const int* pairs, const float* w, const float* upstream, float inv_count, float* df, int m,
+                         int npairs, int h, int wd, int c, void* stream);
+int srhip_maxpool3x3s2_bwd(const float* x, const float* dy, const float* residual, float* dx, int n, int h, int w, int c, int relu,
+                           void* stream);
+int srhip_lpips_stem_bwd(const float* g, const float* w_hwio, float* dx, int m, int h, int w, int normalize, void* stream);
 
 /* ---- torch.optim.Adam (sradsgan.py:724-725, step at :858 and :887) over a flat fp32 arena, fused
  *      with the discriminator's weight clip `p.data.clamp_(-c, c)` (:891-892; clip <= 0: none).

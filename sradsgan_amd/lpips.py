@@ -1,5 +1,6 @@
 """LPIPS on the device: the reference's `PerceptualLoss(model='net-lin', net='alex')` (sradsgan.py:561; utils/PerceptualSimilarity/
-__init__.py:13-40, networks_basic.py:27-115, pretrained_networks.py:57-96, weights v0.1), forward only.
+__init__.py:13-40, networks_basic.py:27-115, pretrained_networks.py:57-96, weights v0.1): the metric (`forward`, `pairs`, under no_grad) and
+the same distance as a training loss (`loss`, one autograd node with its own backward kernels).
 
 Structure here, weights from the user -- the precedent of FeatureExtractor.load_torchvision_vgg19: the pretrained AlexNet file is
 torchvision's to download, so `load_torchvision_alexnet` takes its state dict (`features.{0,3,6,8,10}.{weight,bias}`); the five learned
@@ -46,6 +47,42 @@ def tap_sizes(h, w):
     h1, w1 = (h0 - 3) // 2 + 1, (w0 - 3) // 2 + 1
     h2, w2 = (h1 - 3) // 2 + 1, (w1 - 3) // 2 + 1
     return [(h0, w0), (h1, w1), (h2, w2), (h2, w2), (h2, w2)]
+
+
+class _Loss(torch.autograd.Function):
+    """LPIPS.loss as one autograd node: the batch mean of the distances, differentiable in pred alone.  The forward is `pairs` over the
+    stacked [target; pred] batch with the taps kept; the backward walks the backbone down again (see LPIPS.loss)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, model, normalize, mode):
+        n = pred.shape[0]
+        with ops.conv_math(mode):
+            taps = model.feature_taps([target, pred], normalize)
+            dist = model._distances(taps, [(i, n + i) for i in range(n)])
+        ctx.model, ctx.normalize, ctx.mode, ctx.taps, ctx.image_hw = model, normalize, mode, taps, tuple(pred.shape[2:])
+        return dist.mean().to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        model, taps = ctx.model, ctx.taps
+        n = taps[0].shape[0] // 2
+        pt = model._pairs_tensor([(i, n + i) for i in range(n)], 2 * n, taps[0].device)
+        grad = grad.detach().to(torch.float32).contiguous()
+        conv = lambda i: model.features[i].weight
+        with ops.conv_math(ctx.mode):
+            # each head gradient arrives through its tap's ReLU; the conv chain adds it after masking its own gradient with the same tap
+            hg = [ops.lpips_head_bwd_raw(f, pt, model.lin(k), grad, n * f.shape[2] * f.shape[3]) for k, f in enumerate(taps)]
+            tp = [f[n:] for f in taps]
+            g = ops.conv2d_dgrad_raw(hg[4], conv(10), tuple(tp[3].shape), 1, 1, residual=hg[3], actmask=tp[3])
+            g = ops.conv2d_dgrad_raw(g, conv(8), tuple(tp[2].shape), 1, 1, residual=hg[2], actmask=tp[2])
+            g = ops.conv2d_dgrad_raw(g, conv(6), (n, CHANNELS[1]) + tuple(tp[2].shape[2:]), 1, 1)
+            g = ops.max_pool3x3s2_bwd_raw(tp[1], g, relu=True, residual=hg[1])
+            h1, w1 = (tp[0].shape[2] - 3) // 2 + 1, (tp[0].shape[3] - 3) // 2 + 1
+            g = ops.conv2d_dgrad_raw(g, conv(3), (n, CHANNELS[0], h1, w1), 1, 2)
+            g = ops.max_pool3x3s2_bwd_raw(tp[0], g, relu=True, residual=hg[0])
+            dx = ops.lpips_stem_bwd_raw(g, model._stem_weight(), ctx.image_hw, ctx.normalize)
+        return dx, None, None, None, None
 
 
 class LPIPS(nn.Module):
@@ -150,13 +187,37 @@ class LPIPS(nn.Module):
         if ops.get_conv_math() == 'half':                # a validation metric must not move with the training arithmetic
             with ops.conv_math('bf16x3'):
                 return self.pairs(images, index_pairs, normalize)
-        taps = self.feature_taps(images, normalize)
+        return self._distances(self.feature_taps(images, normalize), index_pairs)
+
+    def _distances(self, taps, index_pairs):
+        """The heads and the finish over computed taps -> float64 [P]."""
         dev = taps[0].device
         pt = self._pairs_tensor(index_pairs, taps[0].shape[0], dev)
         partial = torch.empty(len(taps), pt.shape[0], _hip.lib().srhip_lpips_blocks(), device=dev, dtype=torch.float64)
         for k, f in enumerate(taps):
             ops.lpips_head_raw(f, pt, self.lin(k), partial[k])
         return ops.lpips_finish_raw(partial, [f.shape[2] * f.shape[3] for f in taps])
+
+    def loss(self, pred, target, normalize=True):
+        """The batch mean of forward(pred, target) as a 0-d float32 tensor that trains: one autograd node whose gradient goes to pred
+        alone (the reference's PerceptualLoss is an ordinary differentiable module; here `pairs` stays a no_grad metric and this is the
+        loss).  Backward: the head backward of every tap, conv2d_dgrad down convs 10, 8, 6 and 3 with each tap's ReLU mask and head
+        gradient fused in, the two pool backwards, the stem backward.  A pred pixel whose features are all zero at a tap receives a zero
+        gradient from that tap where torch autograd would produce NaN (the root of a zero norm).  Conv arithmetic follows ops.conv_math,
+        'half' mapped to 'bf16x3' as in `pairs`; the mode of the forward is the mode of the backward.  Under no_grad, or for a pred
+        that does not require grad, this is the forward alone."""
+        if target.requires_grad:
+            raise ValueError('LPIPS.loss: the gradient goes to pred only; detach the target')
+        ops._require_gpu(pred, 'LPIPS.loss')
+        ops._require_gpu(target, 'LPIPS.loss')
+        if pred.shape != target.shape:
+            raise ValueError('LPIPS: shape mismatch %s vs %s' % (tuple(pred.shape), tuple(target.shape)))
+        mode = ops.get_conv_math()
+        mode = 'bf16x3' if mode == 'half' else mode
+        if not (torch.is_grad_enabled() and pred.requires_grad):
+            with ops.conv_math(mode), torch.no_grad():
+                return self.forward(pred, target, normalize).mean().to(torch.float32)
+        return _Loss.apply(pred, target, self, normalize, mode)
 
     def forward(self, pred, target, normalize=True):
         """PerceptualLoss.forward (__init__.py:26-40): pred, target [N,3,H,W], in [0,1] when normalize else in [-1,1] -> float64 [N]."""

@@ -185,6 +185,9 @@ class DRCAN(_trainer.SRADSGAN):
         if self.penalty_type != 'LS' or self.grad_penalty_Lp_norm != 'L2' or self.loss_Lp_norm != 'L1' or self.relative:
             raise NotImplementedError('DRCAN runs the reference defaults: LS penalty, L2 gradient norm, L1 content loss, '
                                       'non-relativistic GAN; SRADSGAN and SRAGAN take the options')
+        if getattr(self, 'weight_lpips', 0.0) > 0:
+            raise NotImplementedError('DRCAN runs the reference defaults: no LPIPS term in the generator loss (weight_lpips = 0); '
+                                      'SRADSGAN and SRAGAN take args.weight_lpips')
 
     def __init__(self, args, train_loader=None, test_loader=None):
         if getattr(args, 'd_norm_type', None) is not None or getattr(args, 'd_attention', False) or getattr(args, 'd_spectralnorm', False):

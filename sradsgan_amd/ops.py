@@ -2802,7 +2802,7 @@ def max_pool2x2_raw(x):
 
 
 def max_pool3x3s2_raw(x):
-    """nn.MaxPool2d(kernel_size=3, stride=2) (AlexNet features[2] / [5]): floor mode, no padding.  Forward only."""
+    """nn.MaxPool2d(kernel_size=3, stride=2) (AlexNet features[2] / [5]): floor mode, no padding.  Its backward: max_pool3x3s2_bwd_raw."""
     _require_gpu(x, 'max_pool3x3s2')
     x = nhwc(x)
     n, c, h, w = x.shape
@@ -2855,7 +2855,62 @@ def lpips_finish_raw(partial, tap_pixels, out=None):
     return out
 
 
-_POOL_IDX = os.environ.get('SRHIP_POOL_IDX', '1') == '1'        # A/B knob: 0 = the max-pool backward re-reads the pool's input
+def lpips_head_bwd_raw(f, pairs, w, upstream, count):
+    """One tap's gradient of the LPIPS head with respect to the pred features, through the tap's ReLU (srhip_lpips_head_bwd).  f:
+    [M,C,h,w] features of all images; pairs: int32 [P,2] on the device, (target index, pred index) per pair; w: [C]; upstream: a
+    float32 device scalar; count: the number of values the mean runs over (N * h * w) -> [P,C,h,w].  A pixel whose pred features are
+    all zero gets zeros (torch autograd yields NaN there)."""
+    _require_gpu(f, 'lpips_head_bwd')
+    f = nhwc(f)
+    m, c, h, wd = f.shape
+    npairs = pairs.shape[0]
+    if pairs.dtype != torch.int32 or not pairs.is_cuda or not pairs.is_contiguous() or w.numel() != c:
+        raise ValueError('lpips_head_bwd: pairs must be a dense int32 [P, 2] device tensor and w must have C elements')
+    if upstream.dtype != torch.float32 or not upstream.is_cuda or upstream.numel() != 1:
+        raise ValueError('lpips_head_bwd: upstream must be a float32 device scalar')
+    df = empty_nhwc(npairs, c, h, wd, f)
+    _hip.check(_hip.lib().srhip_lpips_head_bwd(_p(f), _p(pairs), _p(w.detach().contiguous()), _p(upstream), 1.0 / float(count), _p(df), m,
+                                               npairs, h, wd, c, _stream()), 'lpips_head_bwd')
+    return df
+
+
+def max_pool3x3s2_bwd_raw(x, dy, relu=False, residual=None):
+    """Backward of nn.MaxPool2d(3, 2) in gather form (srhip_maxpool3x3s2_bwd): dx = gather(dy) [* (x > 0)] [+ residual], x the pool's
+    input.  The first maximum of a window in scan order takes its gradient, as in ATen."""
+    _require_gpu(x, 'max_pool3x3s2_bwd')
+    _require_gpu(dy, 'max_pool3x3s2_bwd')
+    x, dy = nhwc(x), nhwc(dy)
+    n, c, h, w = x.shape
+    if h < 3 or w < 3 or tuple(dy.shape) != (n, c, (h - 3) // 2 + 1, (w - 3) // 2 + 1):
+        raise ValueError('max_pool3x3s2_bwd: dy %s is not the pooled shape of x %s' % (tuple(dy.shape), tuple(x.shape)))
+    if residual is not None:
+        _require_gpu(residual, 'max_pool3x3s2_bwd')
+        residual = nhwc(residual)
+        if residual.shape != x.shape:
+            raise ValueError('max_pool3x3s2_bwd: residual %s must have the shape of x %s' % (tuple(residual.shape), tuple(x.shape)))
+    dx = empty_nhwc(n, c, h, w, x)
+    _hip.check(_hip.lib().srhip_maxpool3x3s2_bwd(_p(x), _p(dy), _p(residual), _p(dx), n, h, w, c, int(bool(relu)), _stream()),
+               'maxpool3x3s2_bwd')
+    return dx
+
+
+def lpips_stem_bwd_raw(g, w_hwio, image_hw, normalize=True):
+    """Data gradient of the LPIPS stem back to the image, scaling layer included (srhip_lpips_stem_bwd).  g: [M,64,Ho,Wo], the gradient
+    at the stem conv's output with the ReLU mask applied; w_hwio: the dense [11,11,3,64] weight; image_hw: (H, W) -> [M,3,H,W]."""
+    _require_gpu(g, 'lpips_stem_bwd')
+    g = nhwc(g)
+    h, w = image_hw
+    if tuple(w_hwio.shape) != (11, 11, 3, 64) or not w_hwio.is_contiguous():
+        raise ValueError('lpips_stem_bwd: needs a dense [11, 11, 3, 64] weight')
+    if h < 7 or w < 7 or tuple(g.shape[1:]) != (64,) + _out_hw(h, w, 11, 4, 2):
+        raise ValueError('lpips_stem_bwd: g %s is not the stem output of a %d x %d image' % (tuple(g.shape), h, w))
+    m = g.shape[0]
+    dx = empty_nhwc(m, 3, h, w, g)
+    _hip.check(_hip.lib().srhip_lpips_stem_bwd(_p(g), _p(w_hwio), _p(dx), m, h, w, int(bool(normalize)), _stream()), 'lpips_stem_bwd')
+    return dx
+
+
+_POOL_IDX = os.environ.get('SRHIP_POOL_IDX', '1') == '1'       # A/B knob: 0 = the max-pool backward re-reads the pool's input
 
 
 def max_pool2x2_idx_raw(x):

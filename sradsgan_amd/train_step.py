@@ -82,6 +82,21 @@ def _join_side(stream, side):
     stream.wait_stream(side)
 
 
+def check_lpips_args(lpips, weight_lpips, use_graph):
+    """The LPIPS term's arguments, checked before anything touches the device: the model the step will call, or None when the weight
+    is 0 (then nothing is asked of the model or of the mode)."""
+    if weight_lpips < 0:
+        raise ValueError('TrainStep: weight_lpips must be >= 0, got %r' % (weight_lpips,))
+    if weight_lpips == 0:
+        return None
+    if lpips is None:
+        raise ValueError('TrainStep: weight_lpips = %r needs lpips, a sradsgan_amd.lpips.LPIPS with its weights loaded' % (weight_lpips,))
+    if use_graph:
+        raise ValueError('TrainStep: use_graph=True with weight_lpips > 0 is not supported (eager is the default and the faster path; '
+                         'the LPIPS backward has not been captured)')
+    return lpips
+
+
 class TrainStep:
     _timeline_on = False        # SRHIP_STEP_TIMELINE=1 (set per instance in __init__)
     max_run_ahead = 0
@@ -89,7 +104,10 @@ class TrainStep:
     def __init__(self, generator, discriminator, feature_extractor, lr=2e-4, b1=0.9, b2=0.999,
                  weight_content=1e-2, weight_gan=1e-3, lambda_gp=10.0, clip_value=0.01, use_gp=True,
                  grad_sync=None, use_graph=False, reuse_d_fake=True, overlap_wgrad=True, overlap_d_step=True,
-                 wgrad_stream=None, d_stream=None, penalty_type='LS', grad_penalty_Lp_norm='L2', loss_Lp_norm='L1', relative=False):
+                 wgrad_stream=None, d_stream=None, penalty_type='LS', grad_penalty_Lp_norm='L2', loss_Lp_norm='L1', relative=False,
+                 lpips=None, weight_lpips=0.0):
+        self.lpips = check_lpips_args(lpips, weight_lpips, use_graph)      # None: no LPIPS code is reached
+        self.weight_lpips = float(weight_lpips)
         for name, value, choices in (('penalty_type', penalty_type, ('LS', 'hinge')),                    # main_sradsgan.py:53-56
                                      ('grad_penalty_Lp_norm', grad_penalty_Lp_norm, ('L2', 'L1', 'Linf')),
                                      ('loss_Lp_norm', loss_Lp_norm, ('L1', 'L2'))):
@@ -194,6 +212,11 @@ class TrainStep:
             return self._compute_shared(imgs_lr, imgs_hr, alpha)
         return self._compute_plain(imgs_lr, imgs_hr, alpha)
 
+    def _lpips_term(self, gen_hr, imgs_hr):
+        """lpips.loss(gen_hr, imgs_hr), the optional perceptual term of the generator's own loss (weight_lpips > 0), on the current
+        stream beside the content term; None when it is off."""
+        return None if self.lpips is None else self.lpips.loss(gen_hr, imgs_hr)
+
     def _compute_plain(self, imgs_lr, imgs_hr, alpha):
         """Every pass of the reference, in the reference's sequence (reuse_d_fake=False; always with spectral-norm layers in D)."""
         G, D, F = self.G, self.D, self.F
@@ -205,12 +228,15 @@ class TrainStep:
         with torch.no_grad():
             real_feat = F(imgs_hr)
         content = self._crit(F(gen_hr), real_feat)
+        lp = self._lpips_term(gen_hr, imgs_hr)
         loss_gan = -ops.mean(D(gen_hr))
         g_real = None
         if self.relative and self._spectral:
             with torch.no_grad():                                 # :842, detached there: a pass of its own (u and v advance), no graph
                 g_real = ops.mean(D(imgs_hr))
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
+        if lp is not None:
+            loss_G = loss_G + self.weight_lpips * lp
         loss_G.backward()
         self._exchange_start('G')
         # ---------------- discriminator (sradsgan.py:865-886) ----------------
@@ -222,6 +248,8 @@ class TrainStep:
         if self.relative:                                         # the logged values only (module docstring)
             loss_gan = loss_gan.detach() + (g_real if g_real is not None else -terms[0].detach())
             loss_G = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * loss_gan
+            if lp is not None:
+                loss_G = loss_G + self.weight_lpips * lp.detach()
         if self.use_gp:
             gp = self.gradient_penalty(imgs_hr, fake, alpha)
             terms.append((1.0 + self.lambda_gp) * gp)             # :639 + :884-886 => 1 + lambda
@@ -230,8 +258,11 @@ class TrainStep:
             gp = torch.zeros((), device=imgs_hr.device)
         self._backward_terms(terms)
         self._exchange_start('D')
-        return dict(loss_G=loss_G.detach(), loss_D=loss_D.detach(), pixel=pixel.detach(),
-                    content=content.detach(), loss_gan=loss_gan.detach(), gp=gp.detach(), gen_hr=fake)
+        out = dict(loss_G=loss_G.detach(), loss_D=loss_D.detach(), pixel=pixel.detach(),
+                   content=content.detach(), loss_gan=loss_gan.detach(), gp=gp.detach(), gen_hr=fake)
+        if lp is not None:
+            out['lpips'] = lp.detach()
+        return out
 
     @staticmethod
     def _backward_terms(terms, inputs=None):
@@ -398,7 +429,10 @@ class TrainStep:
         content = self._crit(fake_feat, real_feat)
         fake_term = ops.mean(d_gen)
         loss_gan = -fake_term.detach()
-        loss_G_own = pixel + self.weight_content * content       # the part of loss_G whose graph is G + VGG
+        loss_G_own = pixel + self.weight_content * content       # the part of loss_G whose graph is G + VGG (+ AlexNet)
+        lp = self._lpips_term(gen_hr, imgs_hr)
+        if lp is not None:
+            loss_G_own = loss_G_own + self.weight_lpips * lp
         loss_G = loss_G_own.detach() + self.weight_gan * loss_gan
         own, neg_fake = loss_G_own.detach(), loss_gan
         self._mark('fwd done (VGG, D(gen), losses)')
@@ -446,6 +480,8 @@ class TrainStep:
             t.record_stream(main)
         out = dict(loss_G=loss_G, loss_D=loss_D, pixel=pixel.detach(), content=content.detach(), loss_gan=loss_gan,
                    gp=gp.detach(), gen_hr=fake)
+        if lp is not None:
+            out['lpips'] = lp.detach()
         if os.environ.get('SRHIP_STEP_DEBUG') == '1':
             out['d_gen'] = d_gen.detach()
         return out
@@ -499,6 +535,9 @@ class TrainStep:
         content = self._crit(fake_feat, real_feat)
         loss_gan = -ops.mean(d_gen)
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
+        lp = self._lpips_term(gen_hr, imgs_hr)
+        if lp is not None:
+            loss_G = loss_G + self.weight_lpips * lp
         logged = dict(loss_G=loss_G.detach(), loss_gan=loss_gan.detach())
 
         def d_forward():
@@ -508,6 +547,8 @@ class TrainStep:
             if self.relative:                                     # the logged values only (module docstring)
                 logged['loss_gan'] = logged['loss_gan'] - terms[0].detach()
                 logged['loss_G'] = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * logged['loss_gan']
+                if lp is not None:
+                    logged['loss_G'] = logged['loss_G'] + self.weight_lpips * lp.detach()
             ops.replay_bn_update(stash)                           # update #3 (the fake pass that is not recomputed)
             fake = gen_hr.detach()
             if self.use_gp:
@@ -559,6 +600,8 @@ class TrainStep:
         self._exchange_start('D')
         out = dict(loss_G=logged['loss_G'], loss_D=loss_D.detach(), pixel=pixel.detach(),
                    content=content.detach(), loss_gan=logged['loss_gan'], gp=gp.detach(), gen_hr=fake)
+        if lp is not None:
+            out['lpips'] = lp.detach()
         if os.environ.get('SRHIP_STEP_DEBUG') == '1':
             out['d_gen'] = d_gen.detach()
         return out

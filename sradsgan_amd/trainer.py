@@ -58,7 +58,10 @@ def default_args(**overrides):
              degrade_eval=False,
              # not in main_sradsgan.py: validation numbers by the papers' protocol (sradsgan_amd.metrics) beside the reference trainer's
              # own; 'reference' = nothing new runs.  eval_crop_border None = scale_factor
-             eval_protocol='reference', eval_crop_border=None, eval_y_channel=True)
+             eval_protocol='reference', eval_crop_border=None, eval_y_channel=True,
+             # not in main_sradsgan.py: weight_lpips * LPIPS(gen_hr, imgs_hr) in the generator's loss (lpips.LPIPS.loss; needs the
+             # weights of lpips_alexnet + lpips_lin, or set_lpips); 0.0 = no LPIPS code runs in the step
+             weight_lpips=0.0)
     d.update(overrides)
     return argparse.Namespace(**d)
 
@@ -165,6 +168,9 @@ class SRADSGAN(object):
                                      ('loss_Lp_norm', self.loss_Lp_norm, ('L1', 'L2'))):
             if value not in choices:
                 raise ValueError('--%s must be one of %s, got %r' % (name, choices, value))
+        self.weight_lpips = getattr(args, 'weight_lpips', 0.0)
+        if isinstance(self.weight_lpips, bool) or not isinstance(self.weight_lpips, (int, float)) or not self.weight_lpips >= 0:
+            raise ValueError('args.weight_lpips must be a number >= 0, got %r' % (self.weight_lpips,))
         self._check_loss_options()
         self.attention = attention_ablation(args)
         self.eval_protocol = evaluation_protocol(args)          # None, or the papers' protocol beside the reference's (validation)
@@ -266,11 +272,20 @@ class SRADSGAN(object):
             if getattr(self, 'grad_sync', None) is None:
                 self.grad_sync = dp.GradSync(self.world)
             self._alpha_rng = np.random.RandomState(1234 + self.rank)                           # alpha drawn per rank
+        loss_lpips = None
+        if self.weight_lpips > 0:                       # the perceptual term of the generator's loss: the metric's model, as a loss
+            loss_lpips = self._lpips_model()
+            if loss_lpips is None:
+                raise ValueError('args.weight_lpips = %r needs LPIPS weights: args.lpips_alexnet + args.lpips_lin, or set_lpips(model) '
+                                 'before training' % (self.weight_lpips,))
+            if self.world > 1:
+                dp.broadcast_module(loss_lpips, 0)
         self.step = TrainStep(self.generator, self.discriminator, self.feature_extractor, lr=self.lr, b1=self.b1, b2=self.b2,
                               weight_content=self.weight_content, weight_gan=self.weight_gan, lambda_gp=self.lambda_gp,
                               clip_value=self.clip_value, use_gp=bool(self.gp), grad_sync=getattr(self, 'grad_sync', None),
                               penalty_type=self.penalty_type, grad_penalty_Lp_norm=self.grad_penalty_Lp_norm,
-                              loss_Lp_norm=self.loss_Lp_norm, relative=bool(self.relative))
+                              loss_Lp_norm=self.loss_Lp_norm, relative=bool(self.relative), lpips=loss_lpips,
+                              weight_lpips=float(self.weight_lpips))
 
     def _batch(self, item, test=False):
         """(lr, hr, bc) device float tensors from a loader item: the reference's 4-tuple, a uint8 HR batch [B,H,W,3],
@@ -342,6 +357,8 @@ class SRADSGAN(object):
                 if (i + 1) % self.sample_interval == 0 or i == 0:                               # host reads only at log cadence
                     lg, ld = float(out['loss_G']), float(out['loss_D'])
                     self.log_dict['loss_G'], self.log_dict['loss_D'] = lg, ld
+                    if 'lpips' in out:                                                          # only with args.weight_lpips > 0
+                        self.log_dict['lpips'] = float(out['lpips'])
                     rlt = OrderedDict(model=self.model_name, epoch=epoch, iters=step_count, time=time.time() - start_time)
                     rlt.update(self.log_dict)
                     if self.rank == 0:

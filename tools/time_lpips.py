@@ -3,7 +3,12 @@ the backbone and 32 pairs): (a) the HIP path (sradsgan_amd.lpips.LPIPS.pairs), (
 same weights (the restatement tests/lpips_ref.py), batched and one image pair at a time as the reference's loop calls it
 (sradsgan.py:1326-1332), and (c) validate.evaluate() at x4 with and without LPIPS, eager and replayed from a hipGraph.  Every shape is
 warmed up first; each figure is timed with device events over a window of at least --window seconds.  One JSON line.
+--loss runs the loss leg instead (LPIPS.loss, the metric as a training term), at the training batch (--batch 32 there): (d) forward +
+backward of LPIPS.loss against eager ATen autograd of the same composition (tests/lpips_loss_ref.py in fp32, channels-last) and (e) the
+benchmark's training step (bench.build_networks, B x 54x54 -> 216x216) with weight_lpips 0 against 1 -- both pairs in one process,
+alternated over --rounds rounds, every window listed so that drift between the rounds shows.
 Usage: python tools/time_lpips.py [--batch 16] [--crop 216] [--window 2] [--no-eager] [--math bf16x3]
+       python tools/time_lpips.py --loss [--batch 32] [--rounds 3] [--no-step] [--math bf16x3]
 (`rocprofv3 --kernel-trace --stats -- python tools/time_lpips.py --no-eager --no-evaluate` for the per-kernel table)."""
 import argparse
 import json
@@ -37,9 +42,63 @@ def timed(fn, window_s, warmup):
     return t0.elapsed_time(t1) / n, n
 
 
+def loss_leg(a, model, sd, lin, dev):
+    """(d) and (e) of the module docstring -> dict."""
+    import statistics
+    from sradsgan_amd import ops
+    from tests import lpips_loss_ref as L
+    B, crop, cl = a.batch, a.crop, torch.channels_last
+    hr = R.hash_image((B, 3, crop, crop), 201).to(dev).contiguous(memory_format=cl)
+    sr = (0.75 * hr + 0.25 * R.hash_image((B, 3, crop, crop), 202).to(dev)).contiguous(memory_format=cl).requires_grad_(True)
+    sdd = {k: (v.to(dev).contiguous(memory_format=cl) if v.dim() == 4 else v.to(dev)) for k, v in sd.items()}
+    lins = [lin['lin%d.model.1.weight' % k].flatten().to(dev) for k in range(5)]
+
+    def hip():
+        sr.grad = None
+        model.loss(sr, hr).backward()
+
+    def eager():
+        sr.grad = None
+        L.loss(sr, hr, sdd, lins, dtype=torch.float32).backward()
+
+    hip_ms, eager_ms = [], []
+    for _ in range(a.rounds):
+        hip_ms.append(timed(hip, a.window, a.warmup)[0])
+        eager_ms.append(timed(eager, a.window, a.warmup)[0])
+    hip()
+    g_hip = sr.grad.clone()
+    eager()
+    rel = float((g_hip - sr.grad).norm() / sr.grad.norm())
+    out = {'metric': 'LPIPS.loss forward + backward, ms (B=%d, %dx%d, %s)' % (B, crop, crop, ops.get_conv_math()),
+           'hip_ms': [round(v, 3) for v in hip_ms], 'eager_autograd_ms': [round(v, 3) for v in eager_ms],
+           'speedup_median': round(statistics.median(eager_ms) / statistics.median(hip_ms), 2), 'grad_rel_2norm_vs_eager': float('%.2e' % rel)}
+    if not a.no_step:
+        import bench
+        from sradsgan_amd.train_step import TrainStep
+        steps = []
+        for weight in (0.0, 1.0):
+            G, D, F = bench.build_networks(dev, seed=20240)
+            steps.append(TrainStep(G, D, F, lpips=model if weight else None, weight_lpips=weight))
+        gen = torch.Generator().manual_seed(1234)
+        hr_s = torch.rand(B, 3, bench.LR_SIDE * bench.SCALE, bench.LR_SIDE * bench.SCALE, generator=gen).to(dev)
+        lr_s = torch.rand(B, 3, bench.LR_SIDE, bench.LR_SIDE, generator=gen).to(dev)
+        alpha = torch.rand(B, 1, 1, 1, generator=gen).to(dev)
+        ms = ([], [])
+        for _ in range(a.rounds):
+            for k in (0, 1):
+                ms[k].append(timed(lambda: steps[k](lr_s, hr_s, alpha), a.window, a.warmup)[0])
+        m0, m1 = statistics.median(ms[0]), statistics.median(ms[1])
+        out.update({'step_ms_weight0': [round(v, 2) for v in ms[0]], 'step_ms_weight1': [round(v, 2) for v in ms[1]],
+                    'step_cost_ms_median': round(m1 - m0, 2), 'step_cost_percent': round(100.0 * (m1 - m0) / m0, 2)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--batch', type=int, default=None, help='default 16, with --loss 32')
+    ap.add_argument('--loss', action='store_true', help='the loss leg: LPIPS.loss forward + backward, and the training step with and without it')
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--no-step', action='store_true')
     ap.add_argument('--crop', type=int, default=216)
     ap.add_argument('--scale', type=int, default=4)
     ap.add_argument('--window', type=float, default=2.0)
@@ -48,6 +107,8 @@ def main():
     ap.add_argument('--no-eager', action='store_true')
     ap.add_argument('--no-evaluate', action='store_true')
     a = ap.parse_args()
+    if a.batch is None:
+        a.batch = 32 if a.loss else 16
     from sradsgan_amd import ops, trainer as T, validate as V
     from sradsgan_amd.lpips import LPIPS
     dev = torch.device('cuda:0')
@@ -58,6 +119,10 @@ def main():
     model.load_torchvision_alexnet(sd)
     model.load_lin(lin)
     model = model.to(dev)
+    if a.loss:
+        ops.set_conv_math(a.math)
+        print(json.dumps(loss_leg(a, model, sd, lin, dev)))
+        return
     cl = torch.channels_last
     hr = R.hash_image((B, 3, crop, crop), 201).to(dev).contiguous(memory_format=cl)
     sr = (0.75 * hr + 0.25 * R.hash_image((B, 3, crop, crop), 202).to(dev)).contiguous(memory_format=cl)
