@@ -97,6 +97,33 @@ int srhip_debug_set(int key, int value);
 int srhip_probe_config(int kind, int n, int h, int w, int cin, int cout, int max_pairs);
 int srhip_probe_read(float* ms, int* units, int cap);
 
+/* ---- which kernels the last conv call launched (added within ABI 14; nothing existing changed) -------------------------------- *
+ * No counterpart in the reference: test infrastructure.  The route heuristics (csrc/conv_fast_fprop.hip: choose_fprop_route,
+ * csrc/conv_wgrad_fast.hip: choose_wgrad_route) decide which kernel a geometry runs, and performance work edits exactly those;
+ * a test of a kernel's tile edges must therefore be able to say that its case still reaches that kernel
+ * (tests/test_conv_geometry_gpu.py).  srhip_conv2d_last_route(buf, cap) writes one line per kernel launch of the most recent
+ * srhip_conv2d_* compute call ON THE CALLING THREAD (the record is thread_local: a step launches from two host threads) into buf
+ * (at most cap bytes, always terminated; buf NULL or cap 0: nothing is written) and returns the number of launches; the first 16
+ * are kept.  An entry point that calls another (the _dil forms, _dual, _pool, _res3) shows its own launches beside the inner
+ * call's.  A line reads
+ *     <family> tile=<a>x<b> bn=<n> math=<m> epi=<e> nsplit=<s> cps=<c> phases=<p> grid=<blocks>
+ * family  narrow | dot | reg | patch | patch-ks | patch-pers | patch-pers-pp | dma | legacy | headconv (forward / data gradient),
+ *         rowtap | wdma | wreg | tail1x1 | wflat | wlegacy | wsmallcin | wnarrow (weight gradient), reduce | reduce-scalar |
+ *         wlegacy-reduce | colsum (split-K reduces, bias column sum), dil-gather | dil-scatter
+ * tile    BM x BN of the GEMM tile; PH x PW output pixels for the patch family; sub-sums x problems for the reduces; rows x
+ *         columns of a sub-image for the dilated passes
+ * bn      patch family: destination channels per tile; reg: source channels per K chunk (16 / 32); wdma / wreg: pixels per K
+ *         chunk; rowtap: the paired-tail remainder (0: no paired tails); narrow / wnarrow: destination channels compiled for;
+ *         dil-*: the dilation
+ * math    0 fp32 products, 1 split-bf16, 2 one bf16 product, 3 one fp16 product
+ * epi     the SRHIP_EPI_* set compiled into the kernel, -1: flags read at run time; 0 where a kernel has no epilogue
+ * nsplit, cps   weight gradients: split-K splits per problem and chunks per split as the kernel walks them
+ * phases  dma: phases of a strided data gradient batched into this launch (0: a plain launch); rowtap / wflat: problems of a
+ *         grouped launch (0: one)
+ * The record is plain integers stored beside each launch; the text is formatted in this call.  Nothing in the library reads it,
+ * and it has no effect on routing. */
+int srhip_conv2d_last_route(char* buf, int cap);
+
 /* ---- arithmetic of the conv fprop/dgrad contraction ------------------------------------------ *
  * Replaces the implicit choice torch makes for nn.Conv2d (torch.backends.cudnn.allow_tf32, which the
  * reference leaves at its default).  Inputs, outputs and accumulation are fp32 in both modes.

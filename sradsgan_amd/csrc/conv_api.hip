@@ -184,6 +184,28 @@ int srhip_debug_set(int key, int value) {
   return SRHIP_OK;
 }
 
+/* The kernel launches of the most recent srhip_conv2d_* call on the calling thread, one text line each (conv_internal.h: RouteRec).
+ * Formats here and nowhere else; the launch path stores integers only. */
+int srhip_conv2d_last_route(char* buf, int cap) {
+  static const char* const names[RF_COUNT] = {"narrow", "dot", "reg", "patch", "patch-ks", "patch-pers", "patch-pers-pp", "dma", "legacy", "headconv",
+                                              "rowtap", "wdma", "wreg", "tail1x1", "wflat", "wlegacy", "wsmallcin", "wnarrow",
+                                              "reduce", "reduce-scalar", "wlegacy-reduce", "colsum", "dil-gather", "dil-scatter"};
+  const RouteLog& l = g_route_log;
+  if (buf && cap > 0) {
+    int pos = 0;
+    buf[0] = 0;
+    const int kept = l.n < ROUTE_CAP ? l.n : ROUTE_CAP;
+    for (int i = 0; i < kept && pos < cap - 1; ++i) {
+      const RouteRec& r = l.rec[i];
+      const int wrote = snprintf(buf + pos, (size_t)(cap - pos), "%s tile=%dx%d bn=%d math=%d epi=%d nsplit=%d cps=%d phases=%d grid=%d\n",
+                                 (r.fam >= 0 && r.fam < RF_COUNT) ? names[r.fam] : "?", r.t0, r.t1, r.bn, r.math, r.epi, r.nsplit, r.cps, r.phases, r.grid);
+      if (wrote < 0) break;
+      pos += wrote < cap - pos ? wrote : cap - pos - 1;     // (snprintf truncated: the buffer is full and terminated)
+    }
+  }
+  return l.n;
+}
+
 int srhip_set_conv_math(int mode) {
   SRHIP_REQUIRE(mode == SRHIP_MATH_FP32 || mode == SRHIP_MATH_BF16X3 || mode == SRHIP_MATH_HALF, "set_conv_math: unknown mode");
   g_conv_math = mode;
@@ -225,9 +247,13 @@ int srhip_pack_weight(const float* w, float* packed, int cout, int cin, int kh, 
 int srhip_conv2d_fwd(const float* x, const float* packed, const float* bias, const float* residual,
                      const float* rowscale, const float* chanscale, float* y, int n, int h, int w, int cin, int cout, int kh, int kw,
                      int stride, int pad, int ldx, int ldy, int ldr, float slope, int flags, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && packed && y, "conv2d_fwd: null tensor");
   SRHIP_REQUIRE(n >= 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                 "conv2d_fwd: bad geometry");
+  // (the output size is (h + 2 pad - kh) / stride + 1 in C arithmetic: a negative numerator truncates towards zero, and with stride >= 2 a
+  // filter one pixel larger than the padded image would count as ONE output pixel that the caller's empty tensor does not have)
+  SRHIP_REQUIRE(h + 2 * pad >= kh && w + 2 * pad >= kw, "conv2d_fwd: filter larger than the padded image (empty output)");
   SRHIP_REQUIRE(ldx >= cin && ldy >= cout, "conv2d_fwd: row stride smaller than channel count");
   SRHIP_REQUIRE(!(flags & SRHIP_EPI_BIAS) || bias, "conv2d_fwd: EPI_BIAS without bias");
   SRHIP_REQUIRE(!(flags & SRHIP_EPI_RESIDUAL) || (residual && ldr >= cout), "conv2d_fwd: EPI_RESIDUAL without residual");
@@ -252,6 +278,7 @@ int srhip_conv2d_fwd(const float* x, const float* packed, const float* bias, con
 int srhip_conv2d_fwd_dual(const float* x, const float* packed, const float* bias, const float* residual, const float* rowscale,
                           const float* chanscale, float* y, void* y_pp, int* served, int n, int h, int w, int cin, int cout, int kh,
                           int kw, int stride, int pad, int ldx, int ldy, int ldr, float slope, int flags, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(y_pp && served && (((uintptr_t)y_pp) & 15) == 0 && ldy == cout, "conv2d_fwd_dual: 16-byte aligned plane buffer, dense fp32 output");
   g_dst2_req.pp = y_pp;
   g_dst2_req.served = 0;
@@ -270,6 +297,7 @@ int srhip_conv2d_fwd_dual(const float* x, const float* packed, const float* bias
  * * 64 * 4 bytes.  flags: 0 or SRHIP_EPI_BIAS.                                                                                  */
 int srhip_conv2d_fwd_pool(const float* x, const float* packed, const float* bias, float* y, float* pool, size_t pool_sec_bytes,
                           int* nseg_out, int n, int h, int w, int cin, int cout, int ldx, int ldy, int flags, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && packed && y && pool && nseg_out, "conv2d_fwd_pool: null tensor");
   SRHIP_REQUIRE(cout == 64 && ldy == 64 && n > 0 && h > 0 && w > 0 && cin > 0 && ldx >= cin, "conv2d_fwd_pool: 64 dense destination channels");
   SRHIP_REQUIRE((flags & ~SRHIP_EPI_BIAS) == 0 && (!(flags & SRHIP_EPI_BIAS) || bias), "conv2d_fwd_pool: plain or bias epilogue");
@@ -295,10 +323,12 @@ int srhip_conv2d_fwd_pool(const float* x, const float* packed, const float* bias
 int srhip_conv2d_dgrad(const float* dy, const float* packed, float* dx, const float* residual, const float* actmask,
                        float slope, int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
                        int ldy, int ldx, int ldr, int accumulate, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(dy && packed && dx, "conv2d_dgrad: null tensor");
   SRHIP_REQUIRE(n >= 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                 "conv2d_dgrad: bad geometry");
   SRHIP_REQUIRE(pad <= kh - 1 && pad <= kw - 1, "conv2d_dgrad: pad > kernel-1 unsupported");
+  SRHIP_REQUIRE(h + 2 * pad >= kh && w + 2 * pad >= kw, "conv2d_dgrad: filter larger than the padded image (empty dy)");
   SRHIP_REQUIRE(ldy >= cout && ldx >= cin, "conv2d_dgrad: row stride smaller than channel count");
   SRHIP_REQUIRE(!residual || ldr >= cin, "conv2d_dgrad: residual row stride smaller than channel count");
   if (fast_dgrad_ok(cin, cout, kh, kw)) {
@@ -327,6 +357,7 @@ static int add_unserved_residuals(float* dx, const float* r2, const float* r3, l
 int srhip_conv2d_dgrad_res3(const float* dy, const float* packed, float* dx, const float* residual, const float* residual2,
                             const float* residual3, int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad,
                             void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(residual && (residual2 || residual3), "conv2d_dgrad_res3: residual and at least one more");
   SRHIP_REQUIRE(cin % 4 == 0 && ((((uintptr_t)residual2) | ((uintptr_t)residual3) | ((uintptr_t)dx)) & 15) == 0, "conv2d_dgrad_res3: Cin % 4 == 0, 16-byte aligned tensors");
   g_res_req.r2 = residual2 ? residual2 : residual3;
@@ -340,6 +371,7 @@ int srhip_conv2d_dgrad_res3(const float* dy, const float* packed, float* dx, con
 }
 int srhip_conv2d_dgrad_pp_res3(const void* dy, int dy_pp, const float* packed, float* dx, const float* residual, const float* residual2,
                                const float* residual3, int n, int h, int w, int cin, int cout, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(residual && (residual2 || residual3), "conv2d_dgrad_pp_res3: residual and at least one more");
   SRHIP_REQUIRE(cin % 4 == 0 && ((((uintptr_t)residual2) | ((uintptr_t)residual3)) & 15) == 0, "conv2d_dgrad_pp_res3: Cin % 4 == 0, 16-byte aligned tensors");
   g_res_req.r2 = residual2 ? residual2 : residual3;
@@ -370,9 +402,11 @@ int srhip_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, co
                        const float* xchanscale, int accumulate, void* workspace,
                        size_t workspace_bytes, int n, int h, int w, int cin, int cout, int kh, int kw, int stride,
                        int pad, int ldx, int ldy, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad: null tensor");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                 "conv2d_wgrad: bad geometry");
+  SRHIP_REQUIRE(h + 2 * pad >= kh && w + 2 * pad >= kw, "conv2d_wgrad: filter larger than the padded image (empty dy)");
   SRHIP_REQUIRE(ldx >= cin && ldy >= cout, "conv2d_wgrad: row stride smaller than channel count");
   if (fast_wgrad_ok(cin, cout, kh, kw)) {
     const bool pr = probe_hit(3, n, h, w, cin, cout);
@@ -396,6 +430,7 @@ int srhip_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, co
   if (rc || !db || bias_done) return rc;
   const int ho = (h + 2 * pad - kh) / stride + 1, wo = (w + 2 * pad - kw) / stride + 1;
   SRHIP_REQUIRE(cout % 4 == 0 ? cout <= 1024 : cout <= 256, "conv2d_wgrad: too many output channels for the bias sum");
+  route_note(RF_COLSUM, 0, 0, 0, 0, 0, 0);
   return colsum_launch(dy, db, static_cast<char*>(workspace) + wbytes, (long)n * ho * wo, cout, ldy, as_stream(stream));
 }
 
@@ -408,6 +443,7 @@ int srhip_conv2d_wgrad_multi_ok(int n, int h, int w, int cin, int cout, int kh, 
 int srhip_conv2d_wgrad_multi(int nprob, const float* const* x, const float* const* dy, float* const* dw, float* const* db,
                              int accumulate, void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout,
                              int kh, int kw, int stride, int pad, int ldx, int ldy, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_multi: null pointer table");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && ldx >= cin && ldy >= cout, "conv2d_wgrad_multi: bad geometry");
   SRHIP_REQUIRE(srhip_conv2d_wgrad_multi_ok(n, h, w, cin, cout, kh, kw, stride, pad) >= nprob,
@@ -443,6 +479,7 @@ int srhip_conv2d_pp_ok(int n, int h, int w, int cin, int cout) {
 }
 int srhip_conv2d_fwd_pp(const void* x, int x_pp, const float* packed, const float* bias, void* y, int y_pp, float* pool, size_t pool_sec_bytes,
                         int* nseg_out, int n, int h, int w, int cin, int cout, float slope, int flags, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && packed && y && (x_pp || y_pp), "conv2d_fwd_pp: null tensor / no padded-plane operand");
   SRHIP_REQUIRE(srhip_conv2d_pp_ok(n, h, w, cin, cout), "conv2d_fwd_pp: shape / arithmetic mode not served (srhip_conv2d_pp_ok)");
   SRHIP_REQUIRE((flags & ~(SRHIP_EPI_BIAS | SRHIP_EPI_LRELU)) == 0 && (!(flags & SRHIP_EPI_BIAS) || bias), "conv2d_fwd_pp: bias / LeakyReLU epilogues only");
@@ -477,6 +514,7 @@ int srhip_conv2d_fwd_pp(const void* x, int x_pp, const float* packed, const floa
 }
 int srhip_conv2d_dgrad_pp(const void* dy, int dy_pp, const float* packed, void* dx, int dx_pp, const float* residual, const void* actmask,
                           float slope, int n, int h, int w, int cin, int cout, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(dy && packed && dx && (dy_pp || dx_pp), "conv2d_dgrad_pp: null tensor / no padded-plane operand");
   SRHIP_REQUIRE(srhip_conv2d_pp_ok(n, h, w, cout, cin), "conv2d_dgrad_pp: shape / arithmetic mode not served (srhip_conv2d_pp_ok of the transposed conv)");
   SRHIP_REQUIRE(!(residual && dx_pp), "conv2d_dgrad_pp: a residual needs an fp32 destination");
@@ -498,6 +536,7 @@ size_t srhip_conv2d_pp_sign_bytes(int n, int h, int w, int cout) {
 }
 int srhip_conv2d_fwd_pp_signs(const void* x, int x_pp, const float* packed, const float* bias, void* y_planes, void* signs, size_t sign_bytes,
                               int n, int h, int w, int cin, int cout, float slope, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(signs && bias && (((uintptr_t)signs) & 15) == 0, "conv2d_fwd_pp_signs: bias and a 16-byte aligned sign buffer");
   const size_t need = srhip_conv2d_pp_sign_bytes(n, h, w, cout);
   SRHIP_REQUIRE(need > 0 && sign_bytes >= need, "conv2d_fwd_pp_signs: shape not served / sign buffer smaller than srhip_conv2d_pp_sign_bytes");
@@ -511,6 +550,7 @@ int srhip_conv2d_fwd_pp_signs(const void* x, int x_pp, const float* packed, cons
 }
 int srhip_conv2d_dgrad_pp_signs(const void* dy, int dy_pp, const float* packed, void* dx_planes, const void* signs, size_t sign_bytes, float slope,
                                 int n, int h, int w, int cin, int cout, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(signs && (((uintptr_t)signs) & 15) == 0, "conv2d_dgrad_pp_signs: a 16-byte aligned sign buffer");
   const size_t need = srhip_conv2d_pp_sign_bytes(n, h, w, cin);
   SRHIP_REQUIRE(need > 0 && sign_bytes >= need, "conv2d_dgrad_pp_signs: shape not served / sign buffer smaller than srhip_conv2d_pp_sign_bytes");
@@ -529,6 +569,7 @@ size_t srhip_conv2d_wgrad_pp_workspace(int nprob, int x_pp, int dy_pp, int n, in
 int srhip_conv2d_wgrad_pp(int nprob, const void* const* x, const void* const* dy, int x_pp, int dy_pp, float* const* dw, float* const* db,
                           int accumulate, void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldf,
                           void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_pp: null pointer table");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, "conv2d_wgrad_pp: bad geometry");
   const bool pr = probe_hit(3, n, h, w, cin, cout);
@@ -543,6 +584,7 @@ int srhip_conv2d_wgrad_pp(int nprob, const void* const* x, const void* const* dy
 int srhip_conv2d_wgrad_act(const float* x, const float* dy, const float* y, float slope, float* dw, float* db, void* workspace,
                            size_t workspace_bytes, int n, int h, int w, int cin, int cout, int kh, int kw, int stride,
                            int pad, int ldx, int ldy, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && y && dw && db, "conv2d_wgrad_act: null tensor");
   SRHIP_REQUIRE(!fast_wgrad_ok(cin, cout, kh, kw), "conv2d_wgrad_act: small-channel convs only");
   const size_t need = srhip_conv2d_wgrad_workspace(n, h, w, cin, cout, kh, kw, stride, pad);
@@ -579,12 +621,14 @@ static bool head_mask_args(const void* mask, size_t mask_bytes, int n, int h, in
 int srhip_conv2d_fwd_head_mask(const float* x, const float* packed, const float* bias, float* y, void* mask_out, const void* mask_in,
                                size_t mask_bytes, int n, int h, int w, int cin, int cout, int ldx, int ldy, float slope, int flags,
                                void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(head_mask_args(mask_out ? mask_out : mask_in, mask_bytes, n, h, w, cin, cout),
                 "conv2d_fwd_head_mask: shape not served (srhip_conv2d_head_mask_ok) / record missing, misaligned or smaller than srhip_conv2d_head_mask_bytes");
   return legacy_headconv_fwd_mask(x, packed, bias, y, mask_out, mask_in, n, h, w, cin, cout, ldx, ldy, slope, flags, stream);
 }
 int srhip_conv2d_dgrad_head_mask(const float* dy, const float* packed, float* dx, const void* mask, size_t mask_bytes, float slope, int n,
                                  int h, int w, int cin, int cout, int ldy, int ldx, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(dy && packed && dx, "conv2d_dgrad_head_mask: null tensor");
   SRHIP_REQUIRE(head_mask_args(mask, mask_bytes, n, h, w, cin, cout) && ldy == cout && ldx >= cin,
                 "conv2d_dgrad_head_mask: shape not served (srhip_conv2d_head_mask_ok, dense dy) / record missing, misaligned or too small");
@@ -600,6 +644,7 @@ int srhip_conv2d_dgrad_head_mask(const float* dy, const float* packed, float* dx
 int srhip_conv2d_wgrad_head_mask(const float* x, const float* dy, const void* mask, size_t mask_bytes, float slope, float* dw, float* db,
                                  void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldx, int ldy,
                                  void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_head_mask: null tensor");
   SRHIP_REQUIRE(head_mask_args(mask, mask_bytes, n, h, w, cin, cout),
                 "conv2d_wgrad_head_mask: shape not served (srhip_conv2d_head_mask_ok) / record missing, misaligned or too small");

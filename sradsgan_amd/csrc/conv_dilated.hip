@@ -77,6 +77,7 @@ static int gather(const float* x, int ldx, const float* chanscale, float* xs, in
   const int hs = (h + d - 1) / d, ws = (w + d - 1) / d;
   const long total = (long)n * d * d * hs * ws * (c / 4);
   if (total == 0) return SRHIP_OK;
+  route_note(RF_DIL_GATHER, hs, ws, d, 0, 0, cdiv(total, 256));     // (bn field: the dilation)
   hipLaunchKernelGGL(dil_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, x, ldx, chanscale, xs, n, h, w, hs, ws, d, c / 4);
   return check_launch("conv2d_dil: gather");
 }
@@ -85,6 +86,7 @@ static int scatter(const float* ys, float* y, int ldy, int n, int h, int w, int 
   const int hs = (h + d - 1) / d, ws = (w + d - 1) / d;
   const long total = (long)n * h * w * (c / 4);
   if (total == 0) return SRHIP_OK;
+  route_note(RF_DIL_SCATTER, hs, ws, d, 0, 0, cdiv(total, 256));
   hipLaunchKernelGGL(dil_scatter_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, ys, y, ldy, n, h, w, hs, ws, d, c / 4, accumulate);
   return check_launch("conv2d_dil: scatter");
 }
@@ -110,6 +112,7 @@ size_t srhip_conv2d_dil_workspace(int kind, int n, int h, int w, int cin, int co
 int srhip_conv2d_fwd_dil(const float* x, const float* packed, const float* bias, const float* chanscale, float* y, void* workspace,
                          size_t workspace_bytes, int n, int h, int w, int cin, int cout, int dilation, int ldx, int ldy, float slope,
                          int flags, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && packed && y, "conv2d_fwd_dil: null tensor");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && dilation >= 1 && dilation <= 3, "conv2d_fwd_dil: bad geometry");
   SRHIP_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= cin && ldy >= cout && aligned16(x) && aligned16(y),
@@ -140,6 +143,7 @@ int srhip_conv2d_fwd_dil(const float* x, const float* packed, const float* bias,
 
 int srhip_conv2d_dgrad_dil(const float* dy, const float* packed, float* dx, void* workspace, size_t workspace_bytes, int n, int h, int w,
                            int cin, int cout, int dilation, int ldy, int ldx, int accumulate, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(dy && packed && dx, "conv2d_dgrad_dil: null tensor");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && dilation >= 1 && dilation <= 3, "conv2d_dgrad_dil: bad geometry");
   SRHIP_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= cin && ldy >= cout && aligned16(dy) && aligned16(dx),
@@ -165,6 +169,7 @@ int srhip_conv2d_dgrad_dil(const float* dy, const float* packed, float* dx, void
 
 int srhip_conv2d_wgrad_dil(const float* x, const float* dy, float* dw, float* db, int accumulate, void* workspace, size_t workspace_bytes,
                            int n, int h, int w, int cin, int cout, int dilation, int ldx, int ldy, void* stream) {
+  RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_dil: null tensor");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && dilation >= 1 && dilation <= 3, "conv2d_wgrad_dil: bad geometry");
   SRHIP_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= cin && ldy >= cout && aligned16(x) && aligned16(dy),

@@ -1415,6 +1415,7 @@ int fast_pack_weight(const float* w, float* packed, int cout, int cin, int kh, i
 // ================================================================================================ //
 // host side: choose_fprop_route says which kernel a call takes, launch_fprop launches it
 // ================================================================================================ //
+thread_local RouteLog g_route_log;
 thread_local Dst2Request g_dst2_req;
 thread_local ResRequest g_res_req;
 thread_local PhaseRequest g_phase_req;
@@ -1508,6 +1509,7 @@ static const float* weight_section(const ConvOperands& a, const FastGeom& g, int
 template <int BM, int BN, int WM, int WN, int BK, int MATH = 0>
 static int launch_reg(const ConvOperands& a, const FastGeom& g, hipStream_t st) {
   const int nbm = cdiv(g.M, BM), nbn = cdiv(g.K, BN);
+  route_note(RF_REG, BM, BN, BK, MATH, -1, nbm * nbn);    // (bn field: the K chunk, 16 or 32 source channels)
   hipLaunchKernelGGL((fast_conv_kernel<BM, BN, WM, WN, BK, MATH>), dim3(nbm * nbn), dim3(WM * WN * 64), 0, st, a.src,
                      weight_section(a, g, MATH), a.bias, a.residual, a.rowscale, a.chanscale, a.actmask, a.dst, g, nbm, nbn);
   return check_launch("fast_conv");
@@ -1650,12 +1652,14 @@ static FpropRoute choose_fprop_route(const FastGeom& g, const ConvOperands& a) {
 
 template <int BN, int EPI, int PROD = 0>
 static int launch_patch(const ConvOperands& a, const FastGeom& g, const FpropRoute& r, hipStream_t st) {
+  route_note(RF_PATCH, r.pg.PH, r.pg.PW, BN, PROD + 1, EPI, r.nbm * r.nbn);
   hipLaunchKernelGGL((conv_patch_kernel<BN, EPI, PROD>), dim3(r.nbm * r.nbn), dim3(256), 0, st, a.src, weight_section(a, g, PROD + 1), a.bias,
                      a.residual, a.actmask, a.dst, g, r.pg, r.nbm, r.nbn);
   return check_launch("conv_patch");
 }
 template <int EPI>
 static int launch_patch_ks(const ConvOperands& a, const FastGeom& g, const FpropRoute& r, hipStream_t st) {
+  route_note(RF_PATCH_KS, r.pg.PH, r.pg.PW, 64, 1, EPI, r.nbm * r.nbn);
   hipLaunchKernelGGL((conv_patch_ks_kernel<EPI>), dim3(r.nbm * r.nbn), dim3(256), 0, st, a.src, weight_section(a, g, 1), a.bias, a.residual,
                      a.actmask, a.dst, g, r.pg, r.nbm, r.nbn);
   return check_launch("conv_patch_ks");
@@ -1677,6 +1681,7 @@ static int launch_dma(const ConvOperands& a, const FastGeom& g, const FpropRoute
       g_phase_req.launched = 1;
     }
   }
+  route_note(RF_DMA, 128, BN, 0, MATH, EPI, grid, 0, 0, ps.n);
   hipLaunchKernelGGL((fast_conv_dma_kernel<128, BN, EPI, MATH>), dim3(grid), dim3(256), 0, st, a.src, weight_section(a, g, MATH),
                      a.bias, a.residual, a.rowscale, a.chanscale, a.actmask, a.dst, g, r.nbm, r.nbn, ps);
   return check_launch("fast_conv_dma");
@@ -1728,10 +1733,12 @@ static int launch_fprop(const ConvOperands& a, const FastGeom& g, const FpropRou
       }
       auto k = smask ? (r.nd == 3 ? narrow_conv_kernel<3, true> : narrow_conv_kernel<4, true>)
                      : (r.nd == 3 ? narrow_conv_kernel<3, false> : narrow_conv_kernel<4, false>);
+      route_note(RF_NARROW, 16, 16, r.nd, 0, -1, g.N * th * tw);
       hipLaunchKernelGGL(k, dim3(g.N * th * tw), dim3(256), 0, st, a.src, a.wt, a.bias, a.dst, g, th, tw, lo_h, lo_w, smask);
       return check_launch("narrow_conv");
     }
     case FpropFamily::Dot:
+      route_note(RF_DOT, 4, 1, 0, 0, -1, cdiv(g.M, 4));
       hipLaunchKernelGGL(dot_conv_kernel, dim3(cdiv(g.M, 4)), dim3(256), 0, st, a.src, a.wt, a.bias, a.dst, g);
       return check_launch("dot_conv");
     case FpropFamily::Dma:

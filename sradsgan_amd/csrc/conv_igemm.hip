@@ -600,6 +600,7 @@ template <int MASK>
 static void launch_headconv(dim3 grid, size_t lds, hipStream_t st, int cin, const float* x, const float* packed, const float* bias, float* y,
                             unsigned long long* rec, int n, int h, int w, int cout, int ldx, int ldy, int ldw, float slope, int flags,
                             int rows_per_block, int rows_chunk) {
+  route_note(RF_HEADCONV, rows_per_block, 64, MASK, 0, -1, (int)(grid.x * grid.y));     // (bn field: the activation-record form)
   auto kernel = cin == 1 ? headconv_fwd_kernel<MASK, 1> : (cin == 2 ? headconv_fwd_kernel<MASK, 2> : headconv_fwd_kernel<MASK, 3>);
   hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, x, packed, bias, y, rec, n, h, w, cout, ldx, ldy, ldw, slope, flags, rows_per_block,
                      rows_chunk);
@@ -906,6 +907,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_fprop(const float* src, const float* wt, const float* bias, const float* residual,
                         const float* rowscale, float* dst, const ConvGeom& g, bool vec, hipStream_t st) {
   int blocks = cdiv(g.M, BM) * cdiv(g.K, BN);
+  route_note(RF_LEGACY, BM, BN, vec ? 4 : 1, 0, -1, blocks);     // (bn field: floats per source load)
   if (vec)
     hipLaunchKernelGGL((igemm_fprop_kernel<BM, BN, WM, WN, true>), dim3(blocks), dim3(256), 0, st, src, wt, bias,
                        residual, rowscale, dst, g);
@@ -932,6 +934,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_wgrad(const float* x, const float* dy, float* partial, const ConvGeom& g, int nsplit, int cps,
                         bool va, bool vb, hipStream_t st) {
   int blocks = cdiv(g.K, BM) * cdiv(g.Ktot, BN) * nsplit;
+  route_note(RF_WLEGACY, BM, BN, 0, 0, 0, blocks, nsplit, cps);
 #define SRHIP_WG(VA_, VB_)                                                                                     \
   hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, VA_, VB_>), dim3(blocks), dim3(256), 0, st, x, dy, \
                      partial, g, nsplit, cps)
@@ -1126,6 +1129,9 @@ int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* worksp
     const int rps = cdiv(rows, ns);
     ns = cdiv(rows, rps);
     const bool fuse_bias = db != nullptr && bias_ws != nullptr && bias_done != nullptr;
+    route_note(RF_WSMALLCIN, 64, 32, 0, 0, 0, ybits ? ns : ns * cdiv(cout, 64), ns, rps);     // (cps: image rows per split)
+    route_note(RF_WLEGACY_REDUCE, 1, 1, 0, 0, 0, cdiv((long)cout * g.Ktot, 16), ns);
+    if (fuse_bias) route_note(RF_WLEGACY_REDUCE, 1, 1, 0, 0, 0, cdiv(cout, 16), ns);
     if (ybits)
       hipLaunchKernelGGL(wgrad_smallcin_kernel<true>, dim3(ns, 1), dim3(256), (size_t)32 * 1024, st, x, dy, (const float*)nullptr,
                          static_cast<const unsigned long long*>(ybits), slope, partial, fuse_bias ? bias_ws : nullptr, n, h, w, cin, cout, ldx,
@@ -1149,7 +1155,9 @@ int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* worksp
     const int th = cdiv(h, 16), tw = cdiv(w, 16);
     const int ns = p.nsplit < 256 ? p.nsplit : 256;                   // one 576-thread block per CU; the workspace holds p.nsplit tiles
     const size_t lds_bytes = (size_t)(18 * 18 * 64 + 256 * 4) * sizeof(float);
-#define SRHIP_WN(ND_)                                                                                                    \
+    route_note(RF_WNARROW, 16, 16, cout, 0, 0, ns * (cin / 64), ns);
+    route_note(RF_WLEGACY_REDUCE, 1, 1, 0, 0, 0, cdiv((long)cout * g.Ktot, 16), ns);
+#define SRHIP_WN(ND_)                                                                                                   \
   do {                                                                                                                   \
     static bool attr_set = false;                                                                                        \
     if (!attr_set) {                                                                                                     \
@@ -1182,6 +1190,7 @@ int legacy_conv2d_wgrad(const float* x, const float* dy, float* dw, void* worksp
     rc = launch_wgrad<32, 128, 1, 4>(x, dy, partial, g, p.nsplit, p.chunks_per_split, va, vb, st);
   if (rc) return rc;
   long total = (long)cout * g.Ktot;
+  route_note(RF_WLEGACY_REDUCE, 1, 1, 0, 0, 0, cdiv(total, 16), p.nsplit);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 16)), dim3(256), 0, st, partial, dw, p.nsplit, cout, cin,
                      kh * kw, g.Ktot);
   return check_launch("wgrad_reduce");

@@ -98,6 +98,46 @@ size_t flat_wgrad_workspace(int nprob, int x_pp, int dy_pp, int n, int h, int w,
 int flat_wgrad(int nprob, const void* const* x, const void* const* dy, int x_pp, int dy_pp, float* const* dw, float* const* db, int accumulate,
                void* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, int ldf, void* stream);
 
+// ---- which kernels the last public conv call launched (srhip_conv2d_last_route, conv_api.hip) ------------------------------ //
+// Host-only bookkeeping for the tests: every launch site of the conv files notes one RouteRec of plain integers beside its launch
+// (route_note: a few stores into thread_local memory); text is formatted in the query alone.  Nothing in the library reads it.
+// A public srhip_conv2d_* entry point opens a RouteScope; the OUTERMOST scope on a thread clears the record, so an entry point that
+// calls another (the dilated forms, _dual, _pool, _res3) keeps its own launches beside the inner call's.
+enum RouteFam : int {
+  RF_NARROW, RF_DOT, RF_REG, RF_PATCH, RF_PATCH_KS, RF_PATCH_PERS, RF_PATCH_PERS_PP, RF_DMA, RF_LEGACY, RF_HEADCONV,   // fprop / dgrad
+  RF_ROWTAP, RF_WDMA, RF_WREG, RF_TAIL1X1, RF_WFLAT, RF_WLEGACY, RF_WSMALLCIN, RF_WNARROW,                            // wgrad main launches
+  RF_REDUCE, RF_REDUCE_SCALAR, RF_WLEGACY_REDUCE, RF_COLSUM,                                                           // split-K reduces, bias column sum
+  RF_DIL_GATHER, RF_DIL_SCATTER,
+  RF_COUNT
+};
+struct RouteRec {
+  int fam;
+  int t0, t1;        // tile: BM x BN; PH x PW for the patch family; sub-sums x problems for a reduce; hs x ws for the dilated passes
+  int bn;            // destination channels per tile where t0 x t1 is not BM x BN (patch family), else 0
+  int math;          // 0 fp32 products, 1 split-bf16, 2 one bf16 product, 3 one fp16 product
+  int epi;           // the epilogue variant compiled in (-1: flags read at run time); 0 where the kernel has none
+  int nsplit, cps;   // weight gradients: split-K splits and chunks per split
+  int phases;        // LDS-DMA kernel: phases of a strided data gradient batched into this launch (0: a plain launch)
+  int grid;          // blocks launched
+};
+constexpr int ROUTE_CAP = 16;
+struct RouteLog {
+  int n = 0, depth = 0;    // n counts every launch; the first ROUTE_CAP are kept
+  RouteRec rec[ROUTE_CAP];
+};
+extern thread_local RouteLog g_route_log;
+struct RouteScope {
+  RouteScope() { if (g_route_log.depth++ == 0) g_route_log.n = 0; }
+  ~RouteScope() { --g_route_log.depth; }
+  RouteScope(const RouteScope&) = delete;
+  RouteScope& operator=(const RouteScope&) = delete;
+};
+inline void route_note(int fam, int t0, int t1, int bn, int math, int epi, int grid, int nsplit = 0, int cps = 0, int phases = 0) {
+  RouteLog& l = g_route_log;
+  if (l.n < ROUTE_CAP) l.rec[l.n] = RouteRec{fam, t0, t1, bn, math, epi, nsplit, cps, phases, grid};
+  ++l.n;
+}
+
 // column sums (elementwise.hip), used for the bias gradient on the generic path
 size_t colsum_workspace_bytes(long rows, int c);
 int colsum_launch(const float* dy, float* db, void* workspace, long rows, int c, int ld, hipStream_t st);

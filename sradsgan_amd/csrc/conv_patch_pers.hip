@@ -653,6 +653,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
 #define SRHIP_PPX(BN_, EPI_, POOL_, SRC_, DST_, PO_, PS_)                                                                        \
   do {                                                                                                                           \
     if ((g.res2 || g.res3) && !(DST_)) g_res_req.served = 1;                                                                     \
+    route_note(RF_PATCH_PERS_PP, pg.PH, pg.PW, BN_, 1, EPI_, pgrid);                                                             \
     hipLaunchKernelGGL((conv_patch_pers_kernel<BN_, EPI_, 0, POOL_, SRC_, DST_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
                        residual, actmask, dst, g, pg, nbm, nbn, pdbu, ndst16, PO_, PS_);                                         \
     return check_launch("conv_patch_pers_pp");                                                                                   \
@@ -664,6 +665,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
       g_sign_req.served = 1;
 #define SRHIP_PPS(EPI_, SRC_, SG_)                                                                                              \
   do {                                                                                                                         \
+    route_note(RF_PATCH_PERS_PP, pg.PH, pg.PW, 128, 1, EPI_, pgrid);                                                           \
     hipLaunchKernelGGL((conv_patch_pers_kernel<128, EPI_, 0, 0, SRC_, 1, SG_>), dim3(pgrid), dim3(256), 0, st, src, wsplit, bias, \
                        residual, words, dst, g, pg, nbm, nbn, pdbu, ndst16, nullptr, 0u);                                      \
     return check_launch("conv_patch_pers_pp_signs");                                                                           \
@@ -729,6 +731,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
 #define SRHIP_PP(BN_, EPI_, PROD_)                                                                                      \
   do {                                                                                                                  \
     if (g.res2 || g.res3) g_res_req.served = 1;                                                                         \
+    route_note(RF_PATCH_PERS, pg.PH, pg.PW, BN_, PROD_ + 1, EPI_, grid);                                                \
     hipLaunchKernelGGL((conv_patch_pers_kernel<BN_, EPI_, PROD_>), dim3(grid), dim3(256), 0, st, src, wsplit, bias,     \
                        residual, actmask, dst, g, pg, nbm, nbn, db, ndst16, nullptr, 0u);                                                    \
     return check_launch("conv_patch_pers");                                                                             \
@@ -751,6 +754,7 @@ int launch_patch_pers(const float* src, const float* wt, const float* bias, cons
       float* po = g_pool_req.out;
       const unsigned ps = g_pool_req.sec_bytes;
       g_pool_req.served_nseg = nseg;
+      route_note(RF_PATCH_PERS, pg.PH, pg.PW, 64, 1, eflags, grid);
       if (eflags == 0)
         hipLaunchKernelGGL((conv_patch_pers_kernel<64, 0, 0, 1>), dim3(grid), dim3(256), 0, st, src, wsplit, bias, residual, actmask, dst, g,
                            pg, nbm, nbn, db, ndst16, po, ps);

@@ -888,6 +888,7 @@ static bool launch_reduce4(int nprob, const float* const* partial, const float* 
     anydb = anydb || rb.db[k] != nullptr;
   }
   const long total = (long)cout * ktot + (anydb ? cout : 0);
+  route_note(RF_REDUCE, nsplit >= 64 ? 16 : 4, nprob, 0, 0, 0, cdiv(total, 256) * nprob, nsplit);
   if (nsplit >= 64)
     hipLaunchKernelGGL(fast_wgrad_reduce4_kernel<16>, dim3(cdiv(total, 256), nprob), dim3(1024), 0, st, rb, nsplit, cout, cin, khkw, ktot, accumulate, nbias);
   else
@@ -1123,6 +1124,8 @@ static WgradRoute choose_wgrad_route(const WgradGeom& g, int nprob, bool xrow, b
 template <int BM, int CIS>
 static void launch_rowtap(const WgradRoute& r, const WgradGeom& g, const float* x, const float* dy, float* partial, float* bias_partial,
                           const WgradBatch& bt, int blocks, hipStream_t st) {
+  // (tile: BM destination channels x 3 CIS columns; the bn field carries the paired-tail remainder, phases the problems of a grouped launch)
+  route_note(RF_ROWTAP, BM, 3 * CIS, r.tail_rem, r.split ? 1 : 2, 0, blocks, g.nsplit, r.cps, bt.nprob);
   auto k = r.split ? wgrad_rowtap_kernel<BM, CIS, true> : wgrad_rowtap_kernel<BM, CIS, false>;
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, x, dy, partial, bias_partial, g, r.nseg, r.cps, r.tail_rem, bt);
 }
@@ -1130,11 +1133,13 @@ template <int BM, int BN, int WM, int WN>
 static void launch_wgrad_tile(const WgradRoute& r, const WgradGeom& g, const float* x, const float* dy, float* partial, float* bias_partial,
                               const float* xrow, const float* xchan, int blocks, hipStream_t st) {
   if (r.family == WgradFamily::Reg) {
+    route_note(RF_WREG, BM, BN, 16, 0, 0, blocks, g.nsplit, g.chunks_per_split);
     hipLaunchKernelGGL((fast_wgrad_kernel<BM, BN, WM, WN>), dim3(blocks), dim3(256), 0, st, x, dy, partial, bias_partial, xrow, xchan, g);
     return;
   }
   auto k = r.math == 2 ? fast_wgrad_dma_kernel<BM, BN, WM, WN, 16, 2> : r.math == 1 ? fast_wgrad_dma_kernel<BM, BN, WM, WN, 16, 1> :
            r.wbk == 32 ? fast_wgrad_dma_kernel<BM, BN, WM, WN, 32, 0> : fast_wgrad_dma_kernel<BM, BN, WM, WN, 16, 0>;
+  route_note(RF_WDMA, BM, BN, r.math == 0 ? r.wbk : 16, r.math, 0, blocks, g.nsplit, g.chunks_per_split);   // (bn field: pixels per K chunk)
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, x, dy, partial, bias_partial, g);
 }
 // the split-K main launch of a RowTap / Dma / Reg route (bt: the problems of a grouped row-tap launch, empty for one problem)
@@ -1155,6 +1160,7 @@ static void launch_wgrad_main(const WgradRoute& r, const WgradGeom& g, const flo
 static void launch_reduce_scalar(bool sub16, const float* partial, const float* bias_partial, float* dw, float* db, int nsplit, const WgradGeom& g,
                                  int accumulate, hipStream_t st) {
   const long total = (long)g.K * g.Ktot + (db ? g.K : 0);
+  route_note(RF_REDUCE_SCALAR, sub16 ? 16 : 4, 1, 0, 0, 0, cdiv(total, 64), nsplit);
   auto k = sub16 ? fast_wgrad_reduce_kernel<16> : fast_wgrad_reduce_kernel<4>;
   hipLaunchKernelGGL(k, dim3(cdiv(total, 64)), dim3(sub16 ? 1024 : 256), 0, st, partial, bias_partial, dw, db, nsplit, g.K, g.C, g.KH * g.KW, g.Ktot,
                      accumulate);
@@ -1192,6 +1198,7 @@ int fast_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, con
   if (r.family == WgradFamily::Tail1x1) {
     float* bp = db ? bias_partial : nullptr;
     const float* bpp[1] = {bp};
+    route_note(RF_TAIL1X1, 64, 64, 0, 0, 0, r.nsplit, r.nsplit, r.per);     // (cps: pixels per split)
     hipLaunchKernelGGL(wgrad_1x1_scaled_kernel, dim3(r.nsplit), dim3(256), 0, st, x, dy, xrow, xchan, partial, bp, h * w, r.per, r.sp);
     int rc1 = check_launch("wgrad_1x1_scaled");
     if (rc1) return rc1;

@@ -987,6 +987,8 @@ int flat_wgrad(int nprob, const void* const* x, const void* const* dy, int x_pp,
   }
   const int blocks = bt.bpp * nprob;
   const int cfg = p.cfg;
+  // (tile: waves of the kernel x the plan's operand configuration; bn: operands on planes, 1 dy, 2 x, 3 both; phases: problems)
+  route_note(RF_WFLAT, p.kernel, cfg, (x_pp ? 2 : 0) | (dy_pp ? 1 : 0), 1, 0, blocks, g.nsplit, g.cps, nprob);
   if (p.kernel == 8) {
     if (!(x_pp && dy_pp)) {
       if (cfg == 1) hipLaunchKernelGGL((wgrad_flat8_kernel<1, 1>), dim3(blocks), dim3(512), 0, st, g, bt);

@@ -46,6 +46,19 @@ def test_pure_host_entry_points(lib):
     assert lib.srhip_conv2d_wgrad_workspace(2, 54, 54, 64, 256, 3, 3, 1, 1) >= 256 * 576 * 4
 
 
+def test_last_route_query_is_host_only_and_keeps_the_abi_version(lib):
+    """srhip_conv2d_last_route was added within ABI 14 (nothing existing changed): bound, callable without a device, an empty record
+    before any conv call of this thread has launched, the buffer always terminated."""
+    import ctypes
+    from sradsgan_amd import _hip
+    assert lib.srhip_abi_version() == 14
+    assert 'srhip_conv2d_last_route' in _hip.SIGNATURES and 'srhip_conv2d_last_route' in _declared()
+    assert lib.srhip_conv2d_fwd(None, None, None, None, None, None, None, 1, 4, 4, 3, 3, 3, 3, 1, 1, 3, 3, 3, 0.0, 0, None) == -1   # refused: clears, launches nothing
+    buf = ctypes.create_string_buffer(b'\xff' * 64, 64)
+    assert lib.srhip_conv2d_last_route(buf, 64) == 0 and buf.value == b''
+    assert lib.srhip_conv2d_last_route(None, 0) == 0 and lib.srhip_conv2d_last_route(buf, 0) == 0
+
+
 def test_argument_errors_do_not_cross_as_exceptions(lib):
     rc = lib.srhip_conv2d_fwd(None, None, None, None, None, None, None, 1, 4, 4, 3, 3, 3, 3, 1, 1, 3, 3, 3, 0.0, 0, None)
     assert rc == -1 and b'null tensor' in lib.srhip_last_error()

@@ -179,8 +179,40 @@ def _rand(shape, g, scale=1.0):
     return t.contiguous(memory_format=torch.channels_last) if len(shape) == 4 else t
 
 
-def _run(row, g):
-    """Run the row's entry point; return [(name, got, emulate(arith, with_abs) -> (ref, absref), is_discriminating)]."""
+def _nhwc_out(guards, n, c, ld, h, w, prefill=None):
+    """An output of c channels in rows of ld floats, as the [n, c, h, w] view the wrappers take.  guards None: a plain buffer.
+    guards a list (tests/test_conv_geometry_gpu.py): the rows lie in a pointwise_ref.Guarded allocation -- sentinel bands on both
+    sides, body NaN unless prefill (an accumulate destination's previous contents, [n, c, h, w]) -- and the list receives what the
+    caller must find afterwards: bands and the ld - c pad columns intact, every body element written."""
+    if guards is None:
+        buf = torch.full((n, h, w, ld), float('nan'), device=DEV)
+    else:
+        from tests.pointwise_ref import Guarded
+        gd = Guarded((n, h, w, ld), DEV)
+        buf = gd.t
+    view = buf.permute(0, 3, 1, 2)
+    if prefill is not None:
+        view[:, :c] = prefill
+    if guards is not None:
+        guards.append(dict(guard=gd, body=view[:, :c], pad=view[:, c:], accumulate=prefill is not None))
+    return view
+
+
+def _flat_out(guards, shape, prefill=None):
+    """A dense output (a weight or bias gradient) of `shape`, in a Guarded allocation when guards is a list (see _nhwc_out)."""
+    if guards is None:
+        return prefill.clone() if prefill is not None else torch.zeros(shape, device=DEV)
+    from tests.pointwise_ref import Guarded
+    gd = Guarded(shape, DEV)
+    if prefill is not None:
+        gd.t.copy_(prefill)
+    guards.append(dict(guard=gd, body=gd.t, pad=None, accumulate=prefill is not None))
+    return gd.t
+
+
+def _run(row, g, guards=None):
+    """Run the row's entry point; return [(name, got, emulate(arith, with_abs) -> (ref, absref), is_discriminating)].
+    guards: a list -- the outputs the row hands to an entry point itself (row stride / out= forms) then lie in Guarded allocations."""
     from sradsgan_amd import ops
     op, (n, cin, h, w, cout, k, s, p) = row['op'], row['shape']
     d = row.get('d', 1)
@@ -214,8 +246,10 @@ def _run(row, g):
         elif op == 'fwd_pp':
             y = ops.conv2d_fwd_pp_raw(ops.pp_from_f32(x), wt, b, slope=slope)
         else:
-            y = torch.empty(n, cout, h, w, device=DEV).contiguous(memory_format=torch.channels_last)
-            ops.conv2d_dil_fwd_raw(x, cin, wt, b, y, cout, n, h, w, d, slope=slope)
+            ldx, ldy = row.get('ldx', cin), row.get('ldy', cout)
+            xb = _nhwc_out(None, n, cin, ldx, h, w, prefill=x)          # (channels past cin are NaN: they must not be read)
+            y = _nhwc_out(guards, n, cout, ldy, h, w)[:, :cout]
+            ops.conv2d_dil_fwd_raw(xb, ldx, wt, b, y, ldy, n, h, w, d, slope=slope)
 
         def emu(a, with_abs=True):
             r, ar = E.conv_fwd(xs, wt, s, p, a, d, with_abs=with_abs)
@@ -244,8 +278,11 @@ def _run(row, g):
         elif op == 'dgrad_pp':
             dx = ops.conv2d_dgrad_pp_raw(ops.pp_from_f32(dy), wt, residual=res)
         else:
-            dx = torch.empty(n, cin, h, w, device=DEV).contiguous(memory_format=torch.channels_last)
-            ops.conv2d_dil_dgrad_raw(dy, cout, wt, dx, cin, n, h, w, d)
+            ldx, ldy = row.get('ldx', cin), row.get('ldy', cout)
+            yb = _nhwc_out(None, n, cout, ldy, ho, wo, prefill=dy)
+            prev = _rand((n, cin, h, w), g) if row.get('accumulate') else None
+            dx = _nhwc_out(guards, n, cin, ldx, h, w, prefill=prev)[:, :cin]
+            ops.conv2d_dil_dgrad_raw(yb, ldy, wt, dx, ldx, n, h, w, d, accumulate=row.get('accumulate', False))
 
         def emu(a, with_abs=True):
             r, ar = E.conv_dgrad(dy, wt, (n, cin, h, w), s, p, a, d, with_abs=with_abs)
@@ -263,7 +300,7 @@ def _run(row, g):
         if op == 'wgrad':
             if row.get('accumulate'):
                 prev_w, prev_b = _rand(wshape, g).contiguous(), _rand((cout,), g)
-                dw, db = ops.conv2d_wgrad_raw(x, dy, wshape, s, p, True, out=(prev_w.clone(), prev_b.clone()))
+                dw, db = ops.conv2d_wgrad_raw(x, dy, wshape, s, p, True, out=(_flat_out(guards, wshape, prev_w), _flat_out(guards, (cout,), prev_b)))
             else:
                 dw, db = ops.conv2d_wgrad_raw(x, dy, wshape, s, p, row.get('bias', False),
                                               xrowscale=xr.reshape(-1).contiguous() if xr is not None else None, xchanscale=xc)
@@ -281,17 +318,23 @@ def _run(row, g):
             ya = ops.pp_from_f32(dy) if row['ypp'] else dy
             ops.conv2d_wgrad_pp_raw([(xa, ya, dw, db)])
         elif op == 'wgrad_multi':
-            x2, dy2 = _rand(tuple(x.shape), g), _rand(tuple(dy.shape), g)
-            dw, db = torch.zeros(wshape, device=DEV), torch.zeros(cout, device=DEV)
-            dw2, db2 = torch.zeros(wshape, device=DEV), torch.zeros(cout, device=DEV)
-            ops.conv2d_wgrad_multi_raw([(x, dy, dw, db, s, p), (x2, dy2, dw2, db2, s, p)])
+            more = [(_rand(tuple(x.shape), g), _rand(tuple(dy.shape), g)) for _ in range(row.get('nprob', 2) - 1)]
+            zw, zb = torch.zeros(wshape, device=DEV), torch.zeros(cout, device=DEV)
+            items = [(xi, dyi, _flat_out(guards, wshape, zw), _flat_out(guards, (cout,), zb), s, p) for xi, dyi in [(x, dy)] + more]
+            dw, db = items[0][2], items[0][3]
+            ops.conv2d_wgrad_multi_raw(items)
 
-            def emu2(a, with_abs=True):
-                r, ar = E.conv_wgrad(x2, dy2, wshape, s, p, a, with_abs=with_abs)
-                return r, (ar if ar is not None else torch.zeros_like(r))
-            extra = [('dw[1]', dw2, emu2, True), ('db[1]', db2, _colsum_emu(dy2, None), False)]
+            def emu_of(xi, dyi):
+                def emu_i(a, with_abs=True):
+                    r, ar = E.conv_wgrad(xi, dyi, wshape, s, p, a, with_abs=with_abs)
+                    return r, (ar if ar is not None else torch.zeros_like(r))
+                return emu_i
+            for i, (xi, dyi, dwi, dbi, _, _) in enumerate(items[1:], 1):
+                extra += [('dw[%d]' % i, dwi, emu_of(xi, dyi), True), ('db[%d]' % i, dbi, _colsum_emu(dyi, None), False)]
         else:
-            dw, db = ops.conv2d_dil_wgrad_raw(x, cin, dy, cout, wshape, n, h, w, d, with_bias=row.get('bias', False))
+            ldx, ldy = row.get('ldx', cin), row.get('ldy', cout)
+            xb, yb = _nhwc_out(None, n, cin, ldx, h, w, prefill=x), _nhwc_out(None, n, cout, ldy, ho, wo, prefill=dy)
+            dw, db = ops.conv2d_dil_wgrad_raw(xb, ldx, yb, ldy, wshape, n, h, w, d, with_bias=row.get('bias', False))
 
         def emu(a, with_abs=True):
             r, ar = E.conv_wgrad(xs, dy, wshape, s, p, a, d, with_abs=with_abs)
