@@ -66,7 +66,8 @@ int srhip_stream_fork(void* from_stream, void* to_stream);
  *         C <= 128 and the block combine).  The version number stays 14: no existing entry point or layout changed, and the Python binding resolves every
  *         declared symbol by name when it loads the library, so a library without them fails at load time.
  *         The LPIPS metric's passes (srhip_lpips_*, srhip_maxpool3x3s2_fwd) joined the same way: additive, version 14; so did the
- *         backward passes that make it a loss (srhip_lpips_head_bwd, srhip_maxpool3x3s2_bwd, srhip_lpips_stem_bwd). */
+ *         backward passes that make it a loss (srhip_lpips_head_bwd, srhip_maxpool3x3s2_bwd, srhip_lpips_stem_bwd), and the passes of
+ *         the contrastive VGG19 losses (srhip_contrast_*, srhip_maxpool2x2_floor_*). */
 /* Experiment knobs for kernel tuning and for tests that must reach a specific kernel at a small size:
  *   key 0  fprop/dgrad kernel choice: 0 heuristic, -1 force the LDS-DMA kernels, -2 force the patch kernel,
  *          20 / 21 register-staged (exact fp32) kernels only, 23 every launch the patch kernel would take goes to the LDS-DMA kernel,
@@ -907,6 +908,42 @@ int srhip_lpips_head_bwd(const float* f, const int* pairs, const float* w, const
 int srhip_maxpool3x3s2_bwd(const float* x, const float* dy, const float* residual, float* dx, int n, int h, int w, int c, int relu,
                            void* stream);
 int srhip_lpips_stem_bwd(const float* g, const float* w_hwio, float* dx, int m, int h, int w, int normalize, void* stream);
+
+/* Additive, ABI stays 14 -- the contrastive VGG19 losses (contrast.py; reference model/loss.py:121-298).  All tensors channels-last
+ * fp32; exact fp32 elementwise work, float64 reductions in one fixed order per value, no atomics, nothing that crosses samples in the
+ * cosine passes.  A tap `f` holds the features of the stacked batch [a; p; n_1 .. n_N]: (1 + kops) * b images of [h][w][c], kops =
+ * 1 + N <= 9 operands; operand k of sample s is image (k + 1) * b + s.  C % 4 == 0.
+ * maxpool2x2_floor_fwd / _bwd: nn.MaxPool2d(2) for any h, w >= 2: ho = h / 2, wo = w / 2, an odd last row or column belongs to no window
+ *   and gets no gradient; the first maximum of a window wins.  bwd, gather form: dx = gather(dy) [* (x > 0) when relu != 0] [+ residual],
+ *   x [n][h][w][c] the pool's input, residual may be NULL (the contract of srhip_maxpool3x3s2_bwd).
+ * contrast_l1_fwd: partial = double [kops][srhip_contrast_l1_parts()], the sums of |a - x_k| over the tap, every entry written.
+ * contrast_l1_bwd: da [b][h][w][c] = upstream[0] * (coef[0] * sign(a - x_0) - sum_{k >= 1} coef[k] * sign(a - x_k)), sign(0) = 0, 0 where
+ *   a <= 0 (the tap's ReLU).  coef = double [kops] and upstream = float [1], both on the device.
+ * contrast_l1_finish: partial = double [5][kops][parts] of the five taps, tap_counts = host array of the 5 element counts b * h * w * c
+ *   (read during the call), kops >= 2 -> loss[0] = sum_t weight_t * d_ap / (d_an + 1e-7) (ablation != 0: weight_t * d_ap), d_an summed
+ *   over the negatives, weights 1/32 1/16 1/8 1/4 1, and coef = double [5][kops], the (alpha, beta ..) of each tap's backward.
+ * contrast_cos_fwd: per pixel cos_k = (a . x_k) / (max(|a|, 1e-8) max(|x_k|, 1e-8)); partial = double [b][kops][srhip_contrast_cos_parts()],
+ *   the pixel sums of cos_k per sample.
+ * contrast_cos_bwd: da = upstream[0] / (h w) * sum_k gamma[s][k] * d cos_k / d a, 0 where a <= 0; gamma = double [b][kops] on the device.
+ *   d cos / d a_c = x_c / (mx ma) - [|a| > 1e-8] cos a_c / (ma |a|): a zero-norm pixel forms no 0 / 0.
+ * contrast_cos_finish: partial = double [5][b][kops][parts], tap_counts = host array of the 5 h * w.  With E_k = exp(mean cos_k / 0.07):
+ *   form 0 (kops == 2): term = -log(E_0 / (E_1 + 1e-7)), ablation != 0: -log(E_0); form 1: term = -log(E_0 / (sum_{k>=1} E_k + E_0)).
+ *   loss[0] = mean_s sum_t weight_t term; gamma = double [5][b][kops] = weight_t / b * d term / d mean_k; terms = double [5 * b] scratch. */
+int srhip_maxpool2x2_floor_fwd(const float* x, float* y, int n, int h, int w, int c, void* stream);
+int srhip_maxpool2x2_floor_bwd(const float* x, const float* dy, const float* residual, float* dx, int n, int h, int w, int c, int relu,
+                               void* stream);
+int srhip_contrast_l1_parts(void);
+int srhip_contrast_cos_parts(void);
+int srhip_contrast_l1_fwd(const float* f, double* partial, int b, int kops, int h, int w, int c, void* stream);
+int srhip_contrast_l1_bwd(const float* f, const double* coef, const float* upstream, float* da, int b, int kops, int h, int w, int c,
+                          void* stream);
+int srhip_contrast_l1_finish(const double* partial, const long* tap_counts, int kops, int ablation, float* loss, double* coef,
+                             void* stream);
+int srhip_contrast_cos_fwd(const float* f, double* partial, int b, int kops, int h, int w, int c, void* stream);
+int srhip_contrast_cos_bwd(const float* f, const double* gamma, const float* upstream, float* da, int b, int kops, int h, int w, int c,
+                           void* stream);
+int srhip_contrast_cos_finish(const double* partial, const long* tap_counts, int b, int kops, int form, int ablation, float* loss,
+                              double* gamma, double* terms, void* stream);
 
 /* ---- torch.optim.Adam (sradsgan.py:724-725, step at :858 and :887) over a flat fp32 arena, fused
  *      with the discriminator's weight clip `p.data.clamp_(-c, c)` (:891-892; clip <= 0: none).

@@ -188,6 +188,9 @@ class DRCAN(_trainer.SRADSGAN):
         if getattr(self, 'weight_lpips', 0.0) > 0:
             raise NotImplementedError('DRCAN runs the reference defaults: no LPIPS term in the generator loss (weight_lpips = 0); '
                                       'SRADSGAN and SRAGAN take args.weight_lpips')
+        if getattr(self, 'weight_contrast', 0.0) > 0:
+            raise NotImplementedError('DRCAN runs the reference defaults: no contrastive term in the generator loss (weight_contrast = '
+                                      '0); SRADSGAN and SRAGAN take args.weight_contrast')
 
     def __init__(self, args, train_loader=None, test_loader=None):
         if getattr(args, 'd_norm_type', None) is not None or getattr(args, 'd_attention', False) or getattr(args, 'd_spectralnorm', False):

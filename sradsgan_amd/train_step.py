@@ -97,6 +97,22 @@ def check_lpips_args(lpips, weight_lpips, use_graph):
     return lpips
 
 
+def check_contrast_args(contrast, weight_contrast, use_graph):
+    """The contrastive term's arguments, checked like the LPIPS term's: the loss module the step will call, or None when the weight is
+    0 (then nothing is asked of the module, of the mode or of `negatives`)."""
+    if weight_contrast < 0:
+        raise ValueError('TrainStep: weight_contrast must be >= 0, got %r' % (weight_contrast,))
+    if weight_contrast == 0:
+        return None
+    if contrast is None:
+        raise ValueError('TrainStep: weight_contrast = %r needs contrast, one of sradsgan_amd.contrast\'s losses with its VGG19 weights '
+                         'loaded' % (weight_contrast,))
+    if use_graph:
+        raise ValueError('TrainStep: use_graph=True with weight_contrast > 0 is not supported (eager is the default and the faster '
+                         'path; the contrastive backward has not been captured)')
+    return contrast
+
+
 class TrainStep:
     _timeline_on = False        # SRHIP_STEP_TIMELINE=1 (set per instance in __init__)
     max_run_ahead = 0
@@ -105,9 +121,12 @@ class TrainStep:
                  weight_content=1e-2, weight_gan=1e-3, lambda_gp=10.0, clip_value=0.01, use_gp=True,
                  grad_sync=None, use_graph=False, reuse_d_fake=True, overlap_wgrad=True, overlap_d_step=True,
                  wgrad_stream=None, d_stream=None, penalty_type='LS', grad_penalty_Lp_norm='L2', loss_Lp_norm='L1', relative=False,
-                 lpips=None, weight_lpips=0.0):
+                 lpips=None, weight_lpips=0.0, contrast=None, weight_contrast=0.0):
         self.lpips = check_lpips_args(lpips, weight_lpips, use_graph)      # None: no LPIPS code is reached
         self.weight_lpips = float(weight_lpips)
+        self.contrast = check_contrast_args(contrast, weight_contrast, use_graph)      # None: no contrastive code is reached
+        self.weight_contrast = float(weight_contrast)
+        self._negatives = None
         for name, value, choices in (('penalty_type', penalty_type, ('LS', 'hinge')),                    # main_sradsgan.py:53-56
                                      ('grad_penalty_Lp_norm', grad_penalty_Lp_norm, ('L2', 'L1', 'Linf')),
                                      ('loss_Lp_norm', loss_Lp_norm, ('L1', 'L2'))):
@@ -217,6 +236,12 @@ class TrainStep:
         stream beside the content term; None when it is off."""
         return None if self.lpips is None else self.lpips.loss(gen_hr, imgs_hr)
 
+    def _contrast_term(self, gen_hr, imgs_hr):
+        """contrast(gen_hr, imgs_hr, negatives), the optional contrastive term of the generator's own loss (weight_contrast > 0): the
+        super-resolved image is the anchor, the ground truth the positive, this call's `negatives` the negatives; None when it is
+        off."""
+        return None if self.contrast is None else self.contrast(gen_hr, imgs_hr, self._negatives)
+
     def _compute_plain(self, imgs_lr, imgs_hr, alpha):
         """Every pass of the reference, in the reference's sequence (reuse_d_fake=False; always with spectral-norm layers in D)."""
         G, D, F = self.G, self.D, self.F
@@ -229,6 +254,7 @@ class TrainStep:
             real_feat = F(imgs_hr)
         content = self._crit(F(gen_hr), real_feat)
         lp = self._lpips_term(gen_hr, imgs_hr)
+        ct = self._contrast_term(gen_hr, imgs_hr)
         loss_gan = -ops.mean(D(gen_hr))
         g_real = None
         if self.relative and self._spectral:
@@ -237,6 +263,8 @@ class TrainStep:
         loss_G = pixel + self.weight_content * content + self.weight_gan * loss_gan
         if lp is not None:
             loss_G = loss_G + self.weight_lpips * lp
+        if ct is not None:
+            loss_G = loss_G + self.weight_contrast * ct
         loss_G.backward()
         self._exchange_start('G')
         # ---------------- discriminator (sradsgan.py:865-886) ----------------
@@ -250,6 +278,8 @@ class TrainStep:
             loss_G = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * loss_gan
             if lp is not None:
                 loss_G = loss_G + self.weight_lpips * lp.detach()
+            if ct is not None:
+                loss_G = loss_G + self.weight_contrast * ct.detach()
         if self.use_gp:
             gp = self.gradient_penalty(imgs_hr, fake, alpha)
             terms.append((1.0 + self.lambda_gp) * gp)             # :639 + :884-886 => 1 + lambda
@@ -262,6 +292,8 @@ class TrainStep:
                    content=content.detach(), loss_gan=loss_gan.detach(), gp=gp.detach(), gen_hr=fake)
         if lp is not None:
             out['lpips'] = lp.detach()
+        if ct is not None:
+            out['contrast'] = ct.detach()
         return out
 
     @staticmethod
@@ -433,6 +465,9 @@ class TrainStep:
         lp = self._lpips_term(gen_hr, imgs_hr)
         if lp is not None:
             loss_G_own = loss_G_own + self.weight_lpips * lp
+        ct = self._contrast_term(gen_hr, imgs_hr)
+        if ct is not None:
+            loss_G_own = loss_G_own + self.weight_contrast * ct
         loss_G = loss_G_own.detach() + self.weight_gan * loss_gan
         own, neg_fake = loss_G_own.detach(), loss_gan
         self._mark('fwd done (VGG, D(gen), losses)')
@@ -482,6 +517,8 @@ class TrainStep:
                    gp=gp.detach(), gen_hr=fake)
         if lp is not None:
             out['lpips'] = lp.detach()
+        if ct is not None:
+            out['contrast'] = ct.detach()
         if os.environ.get('SRHIP_STEP_DEBUG') == '1':
             out['d_gen'] = d_gen.detach()
         return out
@@ -538,6 +575,9 @@ class TrainStep:
         lp = self._lpips_term(gen_hr, imgs_hr)
         if lp is not None:
             loss_G = loss_G + self.weight_lpips * lp
+        ct = self._contrast_term(gen_hr, imgs_hr)
+        if ct is not None:
+            loss_G = loss_G + self.weight_contrast * ct
         logged = dict(loss_G=loss_G.detach(), loss_gan=loss_gan.detach())
 
         def d_forward():
@@ -549,6 +589,8 @@ class TrainStep:
                 logged['loss_G'] = pixel.detach() + self.weight_content * content.detach() + self.weight_gan * logged['loss_gan']
                 if lp is not None:
                     logged['loss_G'] = logged['loss_G'] + self.weight_lpips * lp.detach()
+                if ct is not None:
+                    logged['loss_G'] = logged['loss_G'] + self.weight_contrast * ct.detach()
             ops.replay_bn_update(stash)                           # update #3 (the fake pass that is not recomputed)
             fake = gen_hr.detach()
             if self.use_gp:
@@ -602,6 +644,8 @@ class TrainStep:
                    content=content.detach(), loss_gan=logged['loss_gan'], gp=gp.detach(), gen_hr=fake)
         if lp is not None:
             out['lpips'] = lp.detach()
+        if ct is not None:
+            out['contrast'] = ct.detach()
         if os.environ.get('SRHIP_STEP_DEBUG') == '1':
             out['d_gen'] = d_gen.detach()
         return out
@@ -677,7 +721,13 @@ class TrainStep:
             if len(self._step_events) > self.max_run_ahead:
                 self._step_events.pop(0).synchronize()
 
-    def __call__(self, imgs_lr, imgs_hr, alpha):
+    def __call__(self, imgs_lr, imgs_hr, alpha, negatives=None):
+        """negatives: the degraded images of the contrastive term ([B,3,H,W], or [B,N,3,H,W] for the N* losses), normally the batch's
+        bicubic up-sampling; read only with weight_contrast > 0."""
+        if self.contrast is not None:
+            if negatives is None:
+                raise ValueError('TrainStep: weight_contrast = %r needs negatives=' % (self.weight_contrast,))
+            self._negatives = negatives
         self._calls += 1
         if not self.use_graph or self._calls == 1:
             # (graph mode: the first iteration runs eagerly -- library, allocator and packed-weight warm-up must happen

@@ -29,6 +29,7 @@ from . import checkpoint as ckpt
 from . import data as sdata
 from . import degrade as sdegrade
 from . import dp
+from . import contrast as scontrast
 from . import lpips as slpips
 from . import ops
 from . import validate as sval
@@ -61,7 +62,11 @@ def default_args(**overrides):
              eval_protocol='reference', eval_crop_border=None, eval_y_channel=True,
              # not in main_sradsgan.py: weight_lpips * LPIPS(gen_hr, imgs_hr) in the generator's loss (lpips.LPIPS.loss; needs the
              # weights of lpips_alexnet + lpips_lin, or set_lpips); 0.0 = no LPIPS code runs in the step
-             weight_lpips=0.0)
+             weight_lpips=0.0,
+             # not in main_sradsgan.py: weight_contrast * the reference's contrastive VGG19 loss (model/loss.py:173-263) of (gen_hr,
+             # imgs_hr, the batch's bicubic image) in the generator's loss; contrast_loss 'l1' = ContrastLoss, 'cosine' =
+             # ContrastCosineLoss; contrast_vgg19 = a torchvision VGG19 state-dict file (or set_contrast); 0.0 = none of it runs
+             weight_contrast=0.0, contrast_loss='l1', contrast_ablation=False, contrast_vgg19=None)
     d.update(overrides)
     return argparse.Namespace(**d)
 
@@ -171,6 +176,15 @@ class SRADSGAN(object):
         self.weight_lpips = getattr(args, 'weight_lpips', 0.0)
         if isinstance(self.weight_lpips, bool) or not isinstance(self.weight_lpips, (int, float)) or not self.weight_lpips >= 0:
             raise ValueError('args.weight_lpips must be a number >= 0, got %r' % (self.weight_lpips,))
+        self.weight_contrast = getattr(args, 'weight_contrast', 0.0)
+        if isinstance(self.weight_contrast, bool) or not isinstance(self.weight_contrast, (int, float)) or not self.weight_contrast >= 0:
+            raise ValueError('args.weight_contrast must be a number >= 0, got %r' % (self.weight_contrast,))
+        self.contrast_loss = getattr(args, 'contrast_loss', 'l1')
+        if self.contrast_loss not in ('l1', 'cosine'):
+            raise ValueError("args.contrast_loss must be 'l1' or 'cosine', got %r" % (self.contrast_loss,))
+        self.contrast_ablation = bool(getattr(args, 'contrast_ablation', False))
+        self.contrast_vgg19 = getattr(args, 'contrast_vgg19', None)                  # a state-dict path, see set_contrast
+        self.contrast = None
         self._check_loss_options()
         self.attention = attention_ablation(args)
         self.eval_protocol = evaluation_protocol(args)          # None, or the papers' protocol beside the reference's (validation)
@@ -280,12 +294,21 @@ class SRADSGAN(object):
                                  'before training' % (self.weight_lpips,))
             if self.world > 1:
                 dp.broadcast_module(loss_lpips, 0)
+        loss_contrast = None
+        if self.weight_contrast > 0:                    # the contrastive term of the generator's loss
+            loss_contrast = self._contrast_model()
+            if loss_contrast is None:
+                raise ValueError('args.weight_contrast = %r needs VGG19 weights: args.contrast_vgg19, or set_contrast(model) before '
+                                 'training' % (self.weight_contrast,))
+            if self.world > 1:
+                dp.broadcast_module(loss_contrast, 0)
         self.step = TrainStep(self.generator, self.discriminator, self.feature_extractor, lr=self.lr, b1=self.b1, b2=self.b2,
                               weight_content=self.weight_content, weight_gan=self.weight_gan, lambda_gp=self.lambda_gp,
                               clip_value=self.clip_value, use_gp=bool(self.gp), grad_sync=getattr(self, 'grad_sync', None),
                               penalty_type=self.penalty_type, grad_penalty_Lp_norm=self.grad_penalty_Lp_norm,
                               loss_Lp_norm=self.loss_Lp_norm, relative=bool(self.relative), lpips=loss_lpips,
-                              weight_lpips=float(self.weight_lpips))
+                              weight_lpips=float(self.weight_lpips), contrast=loss_contrast,
+                              weight_contrast=float(self.weight_contrast))
 
     def _batch(self, item, test=False):
         """(lr, hr, bc) device float tensors from a loader item: the reference's 4-tuple, a uint8 HR batch [B,H,W,3],
@@ -348,10 +371,13 @@ class SRADSGAN(object):
             epoch_loss_G = epoch_loss_D = 0.0
             n_batches = 0
             for i, item in enumerate(self.train_loader):
-                imgs_lr, imgs_hr, _ = self._batch(item)
+                imgs_lr, imgs_hr, imgs_bc = self._batch(item)
                 rng = getattr(self, '_alpha_rng', None) or np.random
                 alpha = torch.from_numpy(rng.random_sample((imgs_hr.size(0), 1, 1, 1))).float().to(self.device)   # :609
-                out = self.step(imgs_lr, imgs_hr, alpha)                                        # :829-892
+                if self.weight_contrast > 0:                                                    # the negative is the batch's bicubic image
+                    out = self.step(imgs_lr, imgs_hr, alpha, negatives=imgs_bc)
+                else:
+                    out = self.step(imgs_lr, imgs_hr, alpha)                                    # :829-892
                 step_count += 1
                 n_batches += 1
                 if (i + 1) % self.sample_interval == 0 or i == 0:                               # host reads only at log cadence
@@ -359,6 +385,8 @@ class SRADSGAN(object):
                     self.log_dict['loss_G'], self.log_dict['loss_D'] = lg, ld
                     if 'lpips' in out:                                                          # only with args.weight_lpips > 0
                         self.log_dict['lpips'] = float(out['lpips'])
+                    if 'contrast' in out:                                                       # only with args.weight_contrast > 0
+                        self.log_dict['contrast'] = float(out['contrast'])
                     rlt = OrderedDict(model=self.model_name, epoch=epoch, iters=step_count, time=time.time() - start_time)
                     rlt.update(self.log_dict)
                     if self.rank == 0:
@@ -391,6 +419,19 @@ class SRADSGAN(object):
         """Use `model` (a loaded sradsgan_amd.lpips.LPIPS, or None to switch the metric off) as `self.lpips_metric` of the reference
         (sradsgan.py:561)."""
         self.lpips = None if model is None else model.to(self.device)
+
+    def set_contrast(self, model):
+        """Use `model` (one of sradsgan_amd.contrast's single-negative losses with its VGG19 weights loaded, or None) as the contrastive
+        term of the generator's loss (args.weight_contrast > 0)."""
+        self.contrast = None if model is None else model.to(self.device)
+
+    def _contrast_model(self):
+        if self.contrast is None and self.contrast_vgg19:
+            cls = scontrast.ContrastLoss if self.contrast_loss == 'l1' else scontrast.ContrastCosineLoss
+            model = cls(ablation=self.contrast_ablation)
+            model.vgg.load_torchvision_vgg19(torch.load(self.contrast_vgg19, map_location='cpu'))
+            self.set_contrast(model)
+        return self.contrast
 
     def _lpips_model(self):
         if self.lpips is None and self.lpips_alexnet:
