@@ -1166,6 +1166,39 @@ int srhip_blur_f32(const float* x, const long* x_strides, const float* kernels_d
 int srhip_degrade_noise_u8(const unsigned char* lr, const float* level_dev, const float* z, float* out, int n, int h, int w, int c,
                            int drawn, unsigned long long seed, unsigned long long step, void* stream);
 
+/* ABI 14 (additive) -- ESRGAN (csrc/esrgan.hip; sradsgan_amd/model/esrgan.py; model/architecture.py, model/sradsgan.py:35-67, :840-878).
+ * Exact fp32 / fp64 arithmetic that ignores srhip_set_conv_math, no atomics, fixed summation orders: re-runs are bit-identical.
+ * Argument errors return SRHIP_ERR_ARG before any launch.
+ *   srhip_gan_loss_fwd_bwd: GANLoss('vanilla' | 'lsgan') against a filled label, mean-reduced, plain or relativistic.  With
+ *     m = relativistic ? mean(b[0 .. count_b)) : 0 and x_i = a[i] - m it forms mean_i f(x_i, label), f = BCE-with-logits in the stable
+ *     form max(x, 0) - x label + log1p(exp(-|x|)) (mode SRHIP_GAN_VANILLA) or (x - label)^2 (SRHIP_GAN_LS).  The mean of b, x_i, f and
+ *     every sum are float64, summed by one 256-thread block (thread t takes i = t, t + 256, .. in order, then a binary tree over t).
+ *     out != NULL: the value, a 0-d float.  gout != NULL (a device scalar, the upstream gradient): da != NULL receives
+ *     gout f'(x_i) / count, db != NULL (relativistic only) the gradient through the mean, -gout sum_i f'(x_i) / (count count_b) in
+ *     every element.  One call may ask for the value, the gradients or both.  A NaN logit gives a NaN value (no fmax), logits of
+ *     +-100 give finite values and gradients.  1 <= count, count_b <= 2^22 (a patch discriminator's B h w).
+ *   srhip_dhead_fwd / _bwd: the dense head of Discriminator_VGG_*: y[b] = b1 + sum_j w1[j] hidden[b][j], hidden = LeakyReLU(b0[j] +
+ *     sum_k w0[j][k] xflat[b][k]) where xflat is the reference's x.view(B, -1) of an NCHW tensor, k = c S S + p.  x is the NHWC
+ *     activation [B][S][S][C] and w0 the [H][C S S] weight as stored: the kernel's addressing resolves the order (element k meets
+ *     x[b][p][c]); no transposed copy and no cached image of either exists.  Summation order of hidden: thread t of 256 runs one fmaf
+ *     chain over the float4 groups t, t + 256, .. of the weight row in ascending k, the 256 chains are added as a binary tree over t,
+ *     the bias is added last; y likewise over j.  The backward takes the LeakyReLU mask from the stored hidden activation (slope > 0)
+ *     and writes dz [B][H] (scratch: the gradient at the first linear's output), dx [B][S][S][C] (NULL: skipped) and dw0, db0, dw1,
+ *     db1 (all four or all NULL), each one fmaf chain per element over ascending b (dx: ascending j).  C % 4 == 0, w0 / dw0 16-byte
+ *     aligned.
+ *   srhip_input_norm_fwd / _bwd: VGGFeatureExtractor's (x - mean[c]) / std[c] on an NHWC image (element e has channel e % c, c <= 4,
+ *     mean / std DEVICE floats [c]) with IEEE subtraction and division, and its backward dx = dy / std[c].                          */
+#define SRHIP_GAN_VANILLA 0
+#define SRHIP_GAN_LS 1
+int srhip_gan_loss_fwd_bwd(const float* a, long count, const float* b, long count_b, int mode, float label, int relativistic,
+                           const float* gout, float* out, float* da, float* db, void* stream);
+int srhip_dhead_fwd(const float* x, const float* w0, const float* b0, const float* w1, const float* b1, float* hidden, float* y, int B,
+                    int C, int S, int H, float slope, void* stream);
+int srhip_dhead_bwd(const float* dy, const float* x, const float* hidden, const float* w0, const float* w1, float* dz, float* dx,
+                    float* dw0, float* db0, float* dw1, float* db1, int B, int C, int S, int H, float slope, void* stream);
+int srhip_input_norm_fwd(const float* x, const float* mean, const float* stdv, float* y, long count, int c, void* stream);
+int srhip_input_norm_bwd(const float* dy, const float* stdv, float* dx, long count, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
