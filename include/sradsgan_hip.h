@@ -201,7 +201,8 @@ int srhip_conv2d_wgrad(const float* x, const float* dy, float* dw_oihw, float* d
  * half arithmetic, enough pixels: srhip_conv2d_wgrad_multi_ok returns the largest group size) in ONE main launch.  The chip wants one full wave of blocks whatever the number
  * of convolutions behind it, so each problem runs with 1 / nprob of the splits: split-K partial traffic, the write burst at the
  * end of the kernel and the reduce shrink by nprob.  x / dy / dw / db are HOST arrays of nprob device pointers (db or db[i] NULL:
- * no bias gradient); workspace as for srhip_conv2d_wgrad of one problem.  The step pairs the weight gradients of consecutive
+ * no bias gradient); workspace as for srhip_conv2d_wgrad of one problem.  The dw[i], and the non-NULL db[i], of one call must be
+ * DISTINCT (each problem's reduce reads, adds and writes its own destination without atomics): a repeated pointer is refused.  The step pairs the weight gradients of consecutive
  * RABs (model/sradsgan.py:222-223 of blocks i and i+1): nothing reads them before the optimiser.                     */
 int srhip_conv2d_wgrad_multi_ok(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad);   /* largest nprob (2..4), 0: not served */
 int srhip_conv2d_wgrad_multi(int nprob, const float* const* x, const float* const* dy, float* const* dw, float* const* db,

@@ -446,6 +446,13 @@ int srhip_conv2d_wgrad_multi(int nprob, const float* const* x, const float* cons
   RouteScope route_scope;
   SRHIP_REQUIRE(x && dy && dw, "conv2d_wgrad_multi: null pointer table");
   SRHIP_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && ldx >= cin && ldy >= cout, "conv2d_wgrad_multi: bad geometry");
+  SRHIP_REQUIRE(nprob >= 2 && nprob <= 4, "conv2d_wgrad_multi: 2..4 problems per launch");
+  // the reduce serves problem blockIdx.y with a plain read-add-write of its own destination: two problems of one launch that share
+  // a destination would race, and one contribution could be lost
+  for (int i = 0; i < nprob; ++i)
+    for (int j = 0; j < i; ++j)
+      SRHIP_REQUIRE(dw[i] != dw[j] && !(db && db[i] && db[i] == db[j]),
+                    "conv2d_wgrad_multi: problems %d and %d share a destination (dw / db must be distinct within one launch)", j, i);
   SRHIP_REQUIRE(srhip_conv2d_wgrad_multi_ok(n, h, w, cin, cout, kh, kw, stride, pad) >= nprob,
                 "conv2d_wgrad_multi: shape / size not served for %d problems (srhip_conv2d_wgrad_multi_ok)", nprob);
   const bool pr = probe_hit(3, n, h, w, cin, cout);

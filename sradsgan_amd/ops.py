@@ -50,7 +50,11 @@ def _skip_param_grads(*params):
 def backward_scope(skip_params=(), stop_at=()):
     """Prunes a backward pass that autograd cannot prune inside custom Functions: parameters listed in
     `skip_params` get no weight gradient (their wgrad kernels are not launched), and the data gradient
-    is not propagated into the tensors listed in `stop_at`."""
+    is not propagated into the tensors listed in `stop_at`.  `skip_params` match by identity, and an op decides once per node: a
+    listed parameter prunes every slot write of its op (a conv's bias with its weight, a norm's beta with its gamma, the parameters
+    of a fused block together); what an op returns to autograd instead is autograd's to drop (backward(inputs=...)).  `stop_at`
+    matches by data_ptr() -- a detached alias of a listed tensor is cut too -- and is read by conv2d's backward only: list the
+    tensor a conv consumes (TrainStep lists the discriminator's input)."""
     prev = (_state.skip_ids, _state.stop_ids)
     _state.skip_ids = frozenset(id(p) for p in skip_params)
     _state.stop_ids = frozenset(t.data_ptr() for t in stop_at)
@@ -1086,7 +1090,15 @@ class _WgradQueue:
             self.flush(key)
 
     def add(self, key, job, group):
-        """`job` waits under `key` for partners of its shape; the `group`-th completes the launch."""
+        """`job` waits under `key` for partners of its shape; the `group`-th completes the launch.  A slot never appears twice in one
+        launch (the problems of a grouped launch read, add and write their destinations unordered): a request for a slot that the
+        waiting list already holds -- a weight used twice in one graph, the same conv in two successive backward calls of one context --
+        sends that list out first, so the two contributions follow each other on the side stream."""
+        q = self.pending.get(key)
+        if q:
+            taken = {t.data_ptr() for j in q for t in (j.gw, j.gb) if t is not None}
+            if job.gw.data_ptr() in taken or (job.gb is not None and job.gb.data_ptr() in taken):
+                self.flush(key)
         q = self.pending.setdefault(key, [])
         q.append(job)
         if len(q) >= group:
@@ -1805,7 +1817,7 @@ class _AttentionTail(Function):
         u, fc1_w, fc2_w, w7, wc, bc, *saved = ctx.saved_tensors
         g = nhwc(g)
         du, dfc1, dfc2, dw7, dwc, dbc = _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, ctx.has_bias,
-                                                       _skip_param_grads())
+                                                       _skip_param_grads(fc1_w, fc2_w, w7, wc, bc))
         dskip = None if _carry_stash(ctx.carry, g) else _passed_through(g)
         return du, dskip, dfc1, dfc2, dw7, dwc, dbc, None, None
 
@@ -1868,7 +1880,7 @@ class _RabBlock(Function):
                                'backward); run the forward again')
         x, t, u, w1, b1, w2, b2, fc1_w, fc2_w, w7, wc, bc, *saved = ctx.saved_tensors
         g = nhwc(g)
-        skip = _skip_param_grads()
+        skip = _skip_param_grads(w1, b1, w2, b2, fc1_w, fc2_w, w7, wc, bc)      # one node, one decision: a listed parameter prunes the block's
         du, dfc1, dfc2, dw7, dwc, dbc = _tail_backward(g, u, fc1_w, fc2_w, w7, wc, bc, saved, ctx.has_b[2], skip)
         dt = conv2d_dgrad_raw(du, w2, tuple(t.shape), 1, 1, None, t, 0.2)          # * LeakyReLU'(t)
         dw2 = db2 = dw1 = db1 = None
@@ -1888,7 +1900,7 @@ class _RabBlock(Function):
         t_pp, ctx.t_pp = ctx.t_pp, None
         x_pp, ctx.x_pp = ctx.x_pp, None
         g = nhwc(g)
-        skip = _skip_param_grads()
+        skip = _skip_param_grads(w1, b1, w2, b2, fc1_w, fc2_w, w7, wc, bc)      # one node, one decision: a listed parameter prunes the block's
         n, _, h, wd = x.shape
         # the tail's backward leaves du as fp32 (the gradient of the block's residual stream) AND as padded planes: conv2's data and
         # weight gradient read the planes (no in-kernel split, no conversion pass)
@@ -2067,7 +2079,7 @@ class _VariantTail(Function):
         n, c, h, w = u.shape
         lib = _hip.lib()
         f32 = dict(device=u.device, dtype=torch.float32)
-        skip_params = _skip_param_grads()
+        skip_params = _skip_param_grads(fc1_w, fc2_w, w7, wc, bc)
         dwc = dbc = None
         if mode == 'CA|SA':
             cat = _variant_cat(u, s, m)                               # the conv's x operand, rebuilt: one pass instead of a saved tensor

@@ -59,6 +59,16 @@ def test_last_route_query_is_host_only_and_keeps_the_abi_version(lib):
     assert lib.srhip_conv2d_last_route(None, 0) == 0 and lib.srhip_conv2d_last_route(buf, 0) == 0
 
 
+def test_grouped_weight_gradient_requires_distinct_destinations_within_the_abi_version(lib):
+    """srhip_conv2d_wgrad_multi refuses a repeated dw / db pointer (a documented requirement added within ABI 14: no signature changed);
+    the check is made on the host tables, before any launch."""
+    import ctypes
+    assert lib.srhip_abi_version() == 14 and 'DISTINCT' in open(HEADER).read()
+    tab = ctypes.c_void_p * 2
+    rc = lib.srhip_conv2d_wgrad_multi(2, tab(256, 512), tab(256, 512), tab(1024, 1024), None, 1, None, 0, 8, 32, 32, 64, 128, 3, 3, 1, 1, 64, 128, None)
+    assert rc == -1 and b'share a destination' in lib.srhip_last_error()
+
+
 def test_argument_errors_do_not_cross_as_exceptions(lib):
     rc = lib.srhip_conv2d_fwd(None, None, None, None, None, None, None, 1, 4, 4, 3, 3, 3, 3, 1, 1, 3, 3, 3, 0.0, 0, None)
     assert rc == -1 and b'null tensor' in lib.srhip_last_error()
